@@ -4,9 +4,15 @@ reference's configs/fcos/fcos_R_50_FPN_1x.yaml) on synthetic COCO-shaped 1333x80
 GPU, one process per GPU (RCCL data parallel when launched under torch.distributed.run).
 
 A step = forward + backward (gradient all-reduce when N>1) + fused SGD step on one resident synthetic batch.
-Prints ONE JSON line on rank 0 (see the task contract); adds `roofline` (dominant conv kernel, measured with HIP
-events recorded on the launch stream during the timed steps) and `cpu_baseline` (the CPU oracle timed on a bounded
-sample: it is test infrastructure and only ever the thing timed beside the product, never part of it).
+Prints ONE JSON line on rank 0 (see the task contract).  A plain run sets up, warms up, times --steps steps and prints
+the line, nothing else.  --full adds what takes runs or steps of its own: `roofline` (dominant conv kernel, measured
+with HIP events recorded on the launch stream during sampled timed steps), `cpu_baseline` (the CPU oracle timed on a
+bounded sample: it is test infrastructure and only ever the thing timed beside the product, never part of it), the
+host-side probes (enqueue lead, three un-timed steps into empty queues) and the device fingerprint.
+
+--dump-outputs DIR writes what the last timed step hands its caller, as float32 .npy files (snapshot_outputs): its
+losses and a fixed, seeded sample of the parameters it updated.  Inputs and initial weights are seeded, so two builds
+run with the same arguments can be compared output for output.
 """
 import argparse
 import json
@@ -128,12 +134,15 @@ def damp_residual_branches(model, gamma=0.25):
 PREFETCH = os.environ.get("SOD_PREFETCH", "1") != "0"
 
 
-def train_step(model, optimizer, data, next_data=None, scheduler=None):
+def train_step(model, optimizer, data, next_data=None, scheduler=None, losses_out=None):
     """One training step.  ``next_data`` (optional) is the batch of the FOLLOWING step: between this step's forward and backward the
     model runs that batch's preprocess + frozen stem/res2 on a side stream (meta-arch ``prefetch``), where the HBM-bound frozen convs
     share the GPU with the MFMA-bound head backward; the next step's forward picks the result up.  Every step still carries exactly one
-    frozen prefix (the next batch's instead of its own)."""
+    frozen prefix (the next batch's instead of its own).  ``losses_out`` (a dict, optional) receives the step's loss tensors."""
     losses = model(data)
+    if losses_out is not None:
+        losses_out.clear()
+        losses_out.update(losses)
     if next_data is not None and PREFETCH and hasattr(model, "prefetch"):
         model.prefetch(next_data)
     total = sum(losses.values())
@@ -405,6 +414,36 @@ def cpu_baseline(model, args):
                       f"fp32 CPU oracle ({Oracle.__name__}){note}, {dt:.1f} s timed ({time.time() - t0:.1f} s in all); host: {os.cpu_count()} logical CPUs, {cpu}"}
 
 
+DUMP_SAMPLE = 1 << 22       # elements of the parameter arena --dump-outputs writes (16 MB in float32)
+
+
+def snapshot_outputs(losses, total, arena):
+    """What the last timed step hands its caller, on the host: its losses (float32 scalars, as computed) and a fixed sample of the
+    parameter arena it updated (float32; the DUMP_SAMPLE indices that a generator seeded with 0 draws from the arena, in increasing order -
+    the whole arena when it is smaller).  Same arguments -> same indices, so two builds compare element for element.  The gradient arena is
+    left out: it is the step's scratch (zeroed by the next step), and its backbone entries depend on the order in which the float-atomic
+    reductions meet - two runs of one build differ there by up to half of a tensor's largest entry (SOD_DETERMINISTIC=1 makes runs
+    bit-identical, at a cost in speed)."""
+    import numpy as np
+
+    out = {k: np.asarray(float(v.detach()), dtype=np.float32) for k, v in losses.items()}
+    out["total_loss"] = np.asarray(float(total.detach()), dtype=np.float32)
+    p = arena.params.detach().reshape(-1)
+    n = p.numel()
+    if n > DUMP_SAMPLE:
+        p = p[torch.from_numpy(np.sort(np.random.default_rng(0).choice(n, DUMP_SAMPLE, replace=False))).to(p.device)]
+    out["params_sample"] = p.float().cpu().numpy()
+    return out
+
+
+def write_outputs(out_dir, arrays):
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 class _StdoutToStderr:
     """RCCL prints a version banner on STDOUT when its first communicator comes up; the contract of this script is ONE JSON line there.
     While the process group is created (eager communicator: ``device_id``) and the first collectives run, file descriptor 1 points to
@@ -562,16 +601,20 @@ def main():
     ap.add_argument("--collective", choices=["all_reduce", "rs_ag"], default=None, help="N > 1: shape of the gradient exchange per bucket - one all-reduce "
                     "(default) or reduce-scatter + all-gather (SURVEY.md 8 e; SOD_GRAD_COLLECTIVE)")
     ap.add_argument("--no-rccl-info", action="store_true", help="N > 1 / rehearsal: do not capture RCCL's INIT log (channels, rings / trees) into config.rccl_info")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--dump-prof", type=int, default=0, help="print the N most expensive (kernel, shape) groups to stderr")
+    ap.add_argument("--full", action="store_true", help="beside the headline: the roofline of sampled timed steps, the CPU oracle baseline, "
+                    "the host probes and the device fingerprint (each can be left out with its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step hands its caller to DIR/<name>.npy: "
+                    "its losses and a fixed, seeded sample of the parameters it updated (snapshot_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: no cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: no roofline (no sampled steps)")
+    ap.add_argument("--dump-prof", type=int, default=0, help="with --full: print the N most expensive (kernel, shape) groups to stderr")
     ap.add_argument("--rccl-rehearsal", action="store_true",
                     help="--gpus 1 only: create a one-rank RCCL process group and issue every data-parallel collective anyway (parameter "
                          "broadcast, normaliser all-reduce, bucketed gradient all-reduce) - exercises the real RCCL path on a one-GPU box")
     ap.add_argument("--hw-queues", type=int, default=0, help="GPU_MAX_HW_QUEUES for this run (default: the runtime's 4 on one GPU, 6 for "
                     "data-parallel ranks and the rehearsal - utils/comm.py:prepare_rank_env)")
-    ap.add_argument("--no-host-probe", action="store_true", help="skip the three un-timed steps after the loop that measure the host's enqueue time "
-                    "into empty queues (profiling runs: the trace then holds exactly warm-up + timed steps)")
+    ap.add_argument("--no-host-probe", action="store_true", help="with --full: skip the three un-timed steps after the loop that measure the host's "
+                    "enqueue time into empty queues (a plain run never takes them: its trace holds exactly warm-up + timed steps)")
     ap.add_argument("--sync-debug", action="store_true", help="diagnostic: torch.cuda.set_sync_debug_mode('warn') during the timed loop - every "
                     "call site that makes the host wait for the device prints a warning with its stack (the step must have none)")
     ap.add_argument("--rehearsal-occupancy", default=None, metavar="WGS:GBPS",
@@ -579,6 +622,12 @@ def main():
                          "the time an 8-rank ring takes at GBPS of bus bandwidth (sod_debug_occupy) - what the step loses while RCCL's channel "
                          "kernels hold CUs; e.g. 32:300")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    # what a plain run leaves out: everything beside the headline figure
+    args.no_roofline = args.no_roofline or not args.full
+    args.no_cpu_baseline = args.no_cpu_baseline or not args.full
+    args.no_host_probe = args.no_host_probe or not args.full
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         spawn_ranks(args, sys.argv[1:])         # does not return
@@ -702,18 +751,21 @@ def main():
     # how far the host runs AHEAD of the device: a device event + a host time stamp at the start of every timed step (a profiler slows the
     # host down, so only the un-profiled run can say); lead_i = (device time of event i) - (host time of its record call)
     lead_ev, lead_host = [], []
-    base_ev = torch.cuda.Event(enable_timing=True)
     torch.cuda.synchronize()
-    base_ev.record()
-    torch.cuda.synchronize()
-    base_host = time.perf_counter()
+    if args.full:
+        base_ev = torch.cuda.Event(enable_timing=True)
+        base_ev.record()
+        torch.cuda.synchronize()
+        base_host = time.perf_counter()
+    last_losses = {} if args.dump_outputs else None
     t0 = time.perf_counter()
     for i in range(args.steps):
-        ev_i = torch.cuda.Event(enable_timing=True)
-        lead_host.append(time.perf_counter())
-        ev_i.record()
-        lead_ev.append(ev_i)
-        if i == (3 * args.steps) // 4 and rank == 0:
+        if args.full:
+            ev_i = torch.cuda.Event(enable_timing=True)
+            lead_host.append(time.perf_counter())
+            ev_i.record()
+            lead_ev.append(ev_i)
+        if args.full and i == (3 * args.steps) // 4 and rank == 0:
             # the shader clock the device reports WHILE the timed loop keeps it busy (a sysfs read: no GPU call, ~50 us of host time; the
             # host runs several steps ahead of the device); read after the loop it is the idle clock
             sclk_mid = device_fingerprint(dev.index or 0, clocks_only=True).get("sclk_active")
@@ -727,7 +779,8 @@ def main():
         # a sampled step computes its own frozen prefix on the main stream (so that its profile holds every conv of a step) and hands
         # none to its successor
         nxt = next(loader)
-        last = train_step(model, optimizer, cur, None if (sample or (i + 1) in sample_at) else nxt, scheduler)
+        last = train_step(model, optimizer, cur, None if (sample or (i + 1) in sample_at) else nxt, scheduler,
+                          last_losses if i == args.steps - 1 else None)
         cur = nxt
     HF.WGRAD_SIDE_STREAM = side_default
     fcos_mod.TOWER_STREAMS = tower_default
@@ -739,7 +792,9 @@ def main():
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     prof, HF.PROFILE = prof_all, None
-    leads = sorted(base_ev.elapsed_time(e) * 1e-3 - (h - base_host) for e, h in zip(lead_ev[2:], lead_host[2:]))
+    # the last timed step's results, before anything else (the host probe's steps) runs on the model
+    outputs = snapshot_outputs(last_losses, last, model.arena) if args.dump_outputs and rank == 0 else None
+    leads = sorted(base_ev.elapsed_time(e) * 1e-3 - (h - base_host) for e, h in zip(lead_ev[2:], lead_host[2:])) if args.full else []
     host_lead_ms = (round(leads[0] * 1e3, 2), round(leads[len(leads) // 2] * 1e3, 2)) if leads else None
     # Host time of ONE step with empty queues (outside the timed region): how long Python + the launch path need to enqueue a step when
     # nothing blocks them.  host_enqueue_ms_per_step above converges to the device's step time once the launch queues are full, so it cannot
@@ -807,10 +862,11 @@ def main():
                                        f"{cfg.SOLVER.WARMUP_ITERS} iterations, stepped every iteration (lr at the last step {optimizer.param_groups[0]['lr']:.3e})"),
                        "host_enqueue_ms_per_step": round(host_dt / args.steps * 1e3, 3),
                        "host_ms_per_step_unblocked": round(min(host_unblocked) * 1e3, 3) if host_unblocked else None,
-                       "host_lead_ms_min_median": host_lead_ms,     # device start of a step minus the host's enqueue time of that start
-                       "device": device_fingerprint(dev.index or 0)},
+                       "host_lead_ms_min_median": host_lead_ms},     # device start of a step minus the host's enqueue time of that start
         }
-        out["config"]["device"]["sclk_active"] = sclk_mid      # sampled at 3/4 of the timed loop (None if sysfs does not expose it)
+        if args.full:
+            out["config"]["device"] = device_fingerprint(dev.index or 0)
+            out["config"]["device"]["sclk_active"] = sclk_mid      # sampled at 3/4 of the timed loop (None if sysfs does not expose it)
         ref_lr = {"fcos": 0.01, "retinanet": 0.01, "reppoints": 0.01, "rrcnn": 0.02}[args.arch]
         if cfg.SOLVER.BASE_LR != ref_lr:        # not the reference configuration's rate: say so in the line (round-3 advisor finding)
             out["config"]["base_lr_note"] = (f"reference config trains at {ref_lr} from an ImageNet checkpoint; random initialisation diverges there "
@@ -854,6 +910,8 @@ def main():
                 print(f"# {kind:10s} NHWCKRs={desc} calls/step {cnt // prof_steps:3d} ms/step {sec / prof_steps * 1e3:7.3f} TF/s {fl / sec / 1e12:7.1f}", file=sys.stderr)
         if world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(model, args)
+        if outputs is not None:
+            write_outputs(args.dump_outputs, outputs)
         print(json.dumps(out), flush=True)
     if world > 1 or rehearsal:
         dist.barrier()

@@ -45,13 +45,42 @@ def test_cfg_eval_tag_and_global_aliasing(tmp_path):
     assert get_cfg() is get_cfg()   # the reference returns the shared global (slender_det/config.py:213-220)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/configs"), reason="reference tree only exists in the build container")
-def test_reference_configs_load_unchanged():
-    import glob
+def _write_reference_configs(root):
+    """Write the reference's config tree (tests/golden/reference_configs.json: the parsed YAML of every file, eval tags kept as
+    {"!eval": expression}) back as YAML files under ``root``, ``_BASE_`` chains and eval tags intact.  -> the written paths."""
+    import json
 
+    import yaml
+
+    class _Eval(str):
+        pass
+
+    class _Dumper(yaml.SafeDumper):
+        pass
+
+    _Dumper.add_representer(_Eval, lambda d, v: d.represent_sequence("tag:yaml.org,2002:python/object/apply:eval", [str(v)], flow_style=True))
+
+    def tagged(v):
+        if isinstance(v, dict):
+            return _Eval(v["!eval"]) if set(v) == {"!eval"} else {k: tagged(x) for k, x in v.items()}
+        return [tagged(x) for x in v] if isinstance(v, list) else v
+
+    with open(os.path.join(os.path.dirname(__file__), "golden", "reference_configs.json")) as f:
+        configs = json.load(f)["configs"]
+    paths = []
+    for rel, tree in sorted(configs.items()):
+        p = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(p), exist_ok=True)
+        with open(p, "w") as f:
+            yaml.dump(tagged(tree), f, Dumper=_Dumper, sort_keys=False)
+        paths.append(p)
+    return paths
+
+
+def test_reference_configs_load_unchanged(tmp_path):
     known_broken = {"base_X_101_32x8d_FPN_2x.yaml", "point_rpn_R_50_FPN_1x.yaml", "rep_points_rpn_R_50_FPN_1x.yaml"}   # broken upstream too
     n = 0
-    for f in glob.glob("/root/reference/configs/**/*.yaml", recursive=True):
+    for f in _write_reference_configs(str(tmp_path / "configs")):
         if os.path.basename(f) in known_broken:
             continue
         fresh_cfg().merge_from_file(f)
@@ -219,24 +248,59 @@ def test_warmup_multistep_lr():
     assert abs(lrs[0] - 1e-5) < 1e-12 and abs(lrs[4] - 0.01) < 1e-12 and abs(lrs[5] - 0.001) < 1e-12 and abs(lrs[8] - 0.0001) < 1e-12
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/train_net.py"), reason="reference tree only exists in the build container")
+# A detectron2-style train_net.py written against the import surface of the reference's (its lines 23-38: detectron2.* and
+# slender_det.*, every name it imports), with the usual Trainer / setup shape.  Under slenderobjdet_amd.dropin it must import and build.
+_DROPIN_TRAIN_NET = '''
+import logging
+import os
+from collections import OrderedDict
+
+import detectron2.utils.comm as comm
+from detectron2.data import MetadataCatalog
+from detectron2.engine import default_argument_parser, hooks, launch
+from detectron2.evaluation import COCOEvaluator as D2COCOEvaluator
+from detectron2.evaluation import DatasetEvaluator, DatasetEvaluators, RotatedCOCOEvaluator, print_csv_format, verify_results
+from detectron2.modeling import GeneralizedRCNNWithTTA
+from slender_det.checkpoint import DetectionCheckpointer
+from slender_det.config import get_cfg
+from slender_det.engine import BaseTrainer, default_setup
+from slender_det.evaluation import COCOEvaluator, inference_on_dataset
+
+
+class Trainer(BaseTrainer):
+    pass
+
+
+def setup(args):
+    cfg = get_cfg()
+    cfg.merge_from_file(args.config_file)
+    cfg.merge_from_list(args.opts)
+    cfg.freeze()
+    default_setup(cfg, args)
+    return cfg
+'''
+
+
 def test_reference_train_net_imports_and_builds_under_dropin(tmp_path):
-    """The reference's own train_net.py (unchanged, read from /root/reference) resolves all its imports against this package and
-    gets as far as cfg setup + Trainer.build_model on CPU."""
+    """A train_net.py with the reference's imports (``detectron2.*`` and ``slender_det.*``, _DROPIN_TRAIN_NET) resolves all of them
+    against this package and gets as far as cfg setup + Trainer.build_model on CPU, on the repository's FCOS config."""
     import runpy
     import sys
 
     import slenderobjdet_amd.dropin  # noqa: F401
     from slenderobjdet_amd.config import get_cfg
 
+    script = tmp_path / "train_net.py"
+    script.write_text(_DROPIN_TRAIN_NET)
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cfg = get_cfg()
     was_frozen = cfg.is_frozen()
     cfg.defrost()
     snapshot = cfg.clone()
     try:
-        ns = runpy.run_path("/root/reference/train_net.py", run_name="reference_train_net")
+        ns = runpy.run_path(str(script), run_name="reference_train_net")
         args = ns["default_argument_parser"]().parse_args(
-            ["--config-file", "/root/reference/configs/fcos/fcos_R_50_FPN_1x.yaml", "--num-gpus", "1", "MODEL.DEVICE", "cpu",
+            ["--config-file", os.path.join(root, "configs", "fcos", "fcos_R_50_FPN_1x.yaml"), "--num-gpus", "1", "MODEL.DEVICE", "cpu",
              "MODEL.WEIGHTS", "", "OUTPUT_DIR", str(tmp_path)])
         cfg2 = ns["setup"](args)
         assert cfg2.MODEL.META_ARCHITECTURE == "FCOSV2" and cfg2.MODEL.FCOS.IOU_LOSS_TYPE == "giou"
@@ -248,6 +312,36 @@ def test_reference_train_net_imports_and_builds_under_dropin(tmp_path):
             cfg[k] = snapshot[k]
         if was_frozen:
             cfg.freeze()
+
+
+def test_bench_output_snapshot_is_a_fixed_float_sample(tmp_path):
+    """bench.py --dump-outputs: the losses as float32 scalars, the same seeded, increasing sample of the parameter arena every time (the
+    whole arena when it is small), float32, under 64 MB in all."""
+    import numpy as np
+
+    from bench import DUMP_SAMPLE, snapshot_outputs, write_outputs
+
+    class Arena:
+        def __init__(self, n):
+            self.params = torch.arange(n, dtype=torch.float32)
+            self.grads = torch.full_like(self.params, float("nan"))        # never dumped: the step's scratch
+
+    losses = {"cls_loss": torch.tensor(1.5), "reg_loss": torch.tensor(0.25, dtype=torch.bfloat16)}
+    big = Arena(DUMP_SAMPLE + 12345)
+    a, b = snapshot_outputs(losses, torch.tensor(1.75), big), snapshot_outputs(losses, torch.tensor(1.75), big)
+    assert sorted(a) == ["cls_loss", "params_sample", "reg_loss", "total_loss"]
+    assert all(np.array_equal(a[k], b[k]) for k in a)
+    p = a["params_sample"]
+    assert p.dtype == np.float32 and p.shape == (DUMP_SAMPLE,) and (np.diff(p) > 0).all() and p[-1] < DUMP_SAMPLE + 12345
+    assert all(a[k].dtype == np.float32 for k in a)
+    assert float(a["total_loss"]) == 1.75 and float(a["reg_loss"]) == 0.25
+    small = snapshot_outputs(losses, torch.tensor(1.75), Arena(1000))
+    assert np.array_equal(small["params_sample"], np.arange(1000, dtype=np.float32))
+    write_outputs(str(tmp_path / "out"), a)
+    files = sorted(os.listdir(tmp_path / "out"))
+    assert files == sorted(k + ".npy" for k in a)
+    assert sum(os.path.getsize(tmp_path / "out" / f) for f in files) <= 64 << 20
+    assert all(np.load(tmp_path / "out" / f).dtype in (np.float32, np.float64) for f in files)
 
 
 def test_bench_gpus_flag_fails_loudly_without_the_gpus():
