@@ -706,6 +706,44 @@ int sod_fcos_regctr_loss_bwd_f32(const float* box_raw, int ld_box, const float* 
                                  const float* grad_reg, const float* grad_ctr, const float* norm, float inv_world, void* dbox, int ld_out,
                                  int ctr_col, void* dctr, int ld_dctr, int dctr_col, float* dscales, float* ws, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Slender-object COCO box evaluation (slender_det/evaluation/cocoeval.py, coco_evaluation.py; host side in
+ * slenderobjdet_amd/evaluation/).  Segments s = k * num_img + i: category k and image i, both in sorted id order.
+ * Parameter arrays marked "host" are read on the host and travel as kernel arguments (T <= 16, A <= 8, T * A <= 64, M <= 8, R <= 128).
+ *
+ * sod_coco_match restates COCOeval.computeIoU + evaluateImg (cocoeval.py:165-192, 242-324) for bbox, maxDet = max_det:
+ *   gt_off [num_seg+1]: segment s owns gts gt_off[s]..gt_off[s+1]-1, in json order; gt_box [G, 4] XYWH float64, gt_crowd [G] (crowd =
+ *   ignored, IoU over the detection's area), gt_ratio [G] float64.  dt_off [num_seg+1]: segment s owns detections dt_off[s].. of a list
+ *   stable-sorted by descending score within each segment; only the first max_det of a segment are matched.  dt_box [N, 4] XYWH float32.
+ *   iou_thr [T] (host), ranges [A, 2] (host) = (lo, hi) ratio ranges.  scratch_off [num_seg]: offset in doubles of the segment's slot in
+ *   `scratch`, needed where sod_coco_match_scratch_doubles(G, max_det) > 0 (the IoU matrix then lives there instead of in LDS).
+ *   Out: dt_matched / dt_ignored [N] bit t * A + a = dtMatches != 0 / dtIgnore of that detection at (iouThr t, range a); entries past
+ *   max_det are not written (caller zeroes).  npig [K, A] += non-ignored gts (caller zeroes).
+ * sod_coco_accumulate restates COCOeval.accumulate (cocoeval.py:326-432) for one ordering of every (range, maxDets): cat_off [K+1]
+ *   bounds category k's entries order[cat_off[k]..] = indices into the segment-ordered arrays (score [N] float32, rank [N] = position in
+ *   its segment, dt_matched / dt_ignored) of one stable sort by (category, -score).  max_dets [M] (host), rec_thr [R] (host) float64.
+ *   Out: precision / scores [T, R, K, A, M], recall [T, K, A, M] float64, written where npig[k, a] > 0 (caller fills -1).
+ * sod_proposal_ar restates _evaluate_predictions_ar (coco_evaluation.py:283-417) with its first `limit` boxes AND classes of an image:
+ *   gt_off [num_img+1] the non-crowd gts of image i (json order): gt_box [G, 4] XYWH float32, gt_cls [G] contiguous class, gt_ratio [G]
+ *   float32.  dt_off [num_img+1] over dt_order [N]: image i's predictions in prediction order, as indices into dt_box [N, 4] XYWH float32
+ *   and dt_cls [N] contiguous class.  K1 = categories + 1 ("all classes" last).  thr [T], ratio_rng [R, 2], area_rng [A, 2] float32
+ *   (host), bounds inclusive.  scratch_off [num_img] in floats where sod_proposal_ar_scratch_floats(G, limit) > 0.
+ *   Out: hits [T, K1, R, A], counts [K1, R, A] int32 (caller zeroes), recalls [T, K1, R, A] float32 = hits / max(counts, 1). */
+long long sod_coco_match_scratch_doubles(int num_gts, int max_det);
+int sod_coco_match(const int* gt_off, const double* gt_box, const unsigned char* gt_crowd, const double* gt_ratio, const int* dt_off,
+                   const float* dt_box, int num_seg, int num_img, int max_det, const double* iou_thr, int T, const double* ranges, int A,
+                   const long long* scratch_off, double* scratch, unsigned long long* dt_matched, unsigned long long* dt_ignored,
+                   int* npig, void* stream);
+int sod_coco_accumulate(const int* cat_off, const long long* order, const float* score, const int* rank,
+                        const unsigned long long* dt_matched, const unsigned long long* dt_ignored, const int* npig, int K, int T, int A,
+                        const int* max_dets, int M, const double* rec_thr, int R, double* precision, double* recall, double* scores,
+                        void* stream);
+long long sod_proposal_ar_scratch_floats(int num_gts, int limit);
+int sod_proposal_ar(const int* gt_off, const float* gt_box, const int* gt_cls, const float* gt_ratio, const int* dt_off,
+                    const long long* dt_order, const float* dt_box, const int* dt_cls, int num_img, int limit, int K1, const float* thr,
+                    int T, const float* ratio_rng, int R, const float* area_rng, int A, const long long* scratch_off, float* scratch,
+                    int* hits, int* counts, float* recalls, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

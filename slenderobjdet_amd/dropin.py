@@ -4,13 +4,15 @@
     python -c "import slenderobjdet_amd.dropin, runpy, sys; sys.argv = ['train_net.py', '--config-file', 'configs/fcos/fcos_R_50_FPN_1x.yaml', \
                '--num-gpus', '8']; runpy.run_path('train_net.py', run_name='__main__')"
 
-Only the training hot path is backed by real code; evaluation / TTA / dataset names resolve to objects that raise
-``NotImplementedError`` when used (out of scope).
+The training hot path and the slender-object COCO box evaluation (slenderobjdet_amd.evaluation) are backed by real code;
+TTA, the rotated evaluator and dataset names resolve to objects that raise ``NotImplementedError`` when used (out of scope,
+SURVEY.md §2.1).
 """
 import sys
 import types
 
 from . import config as _config
+from . import evaluation as _evaluation
 from . import engine as _engine
 from . import modeling as _modeling
 from . import solver as _solver
@@ -23,6 +25,7 @@ from .layers import nn as _nn
 from .modeling import backbone as _backbone
 from .modeling import meta_arch as _meta_arch
 from .modeling import postprocessing as _post
+from .data.catalog import MetadataCatalog as _MetadataCatalog
 from .modeling.shape_spec import ShapeSpec
 from .utils import comm as _comm
 from .utils import registry as _registry
@@ -57,21 +60,6 @@ def _cat(tensors, dim=0):
     return tensors[0] if len(tensors) == 1 else torch.cat(tensors, dim)
 
 
-class _Metadata(dict):
-    def __getattr__(self, k):
-        if k in self:
-            return self[k]
-        raise AttributeError(k)
-
-
-class _MetadataCatalog:
-    _d = {}
-
-    @classmethod
-    def get(cls, name):
-        return cls._d.setdefault(name, _Metadata(name=name, evaluator_type="coco"))
-
-
 def install():
     # ---- detectron2 ----
     _mod("detectron2")
@@ -85,8 +73,9 @@ def install():
          DefaultTrainer=_engine.DefaultTrainer, default_setup=_engine.default_setup)
     sys.modules["detectron2.engine.hooks"] = _hooks
     _mod("detectron2.data", MetadataCatalog=_MetadataCatalog)
-    _mod("detectron2.evaluation", **{n: _unavailable("detectron2.evaluation." + n) for n in
-                                     ("COCOEvaluator", "DatasetEvaluator", "DatasetEvaluators", "RotatedCOCOEvaluator")},
+    _mod("detectron2.evaluation", COCOEvaluator=_evaluation.COCOEvaluator, DatasetEvaluator=_evaluation.DatasetEvaluator,
+         DatasetEvaluators=_evaluation.DatasetEvaluators, inference_context=_evaluation.inference_context,
+         RotatedCOCOEvaluator=_unavailable("detectron2.evaluation.RotatedCOCOEvaluator"),
          print_csv_format=lambda *a, **k: None, verify_results=lambda *a, **k: None)
     _mod("detectron2.structures", Boxes=_structures.Boxes, Instances=_structures.Instances, ImageList=_structures.ImageList,
          pairwise_iou=_structures.pairwise_iou)
@@ -112,8 +101,7 @@ def install():
     _mod("slender_det.solver", build_optimizer=_solver.build_optimizer, get_default_optimizer_params=_solver.get_default_optimizer_params)
     _mod("slender_det.layers", Scale=_nn.Scale, iou_loss=_losses.iou_loss, DFConv2d=_dcn.DFConv2d)
     _mod("slender_det.checkpoint", DetectionCheckpointer=_engine.defaults._Checkpointer)
-    _mod("slender_det.evaluation", COCOEvaluator=_unavailable("slender_det.evaluation.COCOEvaluator"),
-         inference_on_dataset=_unavailable("slender_det.evaluation.inference_on_dataset"))
+    _mod("slender_det.evaluation", COCOEvaluator=_evaluation.COCOEvaluator, inference_on_dataset=_evaluation.inference_on_dataset)
 
 
 install()

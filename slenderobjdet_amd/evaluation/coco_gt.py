@@ -1,0 +1,136 @@
+"""COCO-format ground truth for the evaluator: the json read with the standard library, the gt aspect ratio of
+slender_det/evaluation/coco.py:61-84 (oriented=True), and the flat per-segment arrays the HIP kernels read.
+
+Ratio rules (first that applies): an explicit ``"ratio"`` field; a crowd gt or one without a usable polygon (a polygon needs an
+even number >= 6 of coordinates) takes min(w, h) / max(w, h) of its bbox; otherwise the side ratio min / max of the minimum-area
+rectangle around the convex hull of all its polygons' points (0 for a degenerate rectangle).  The reference computes that rectangle
+with OpenCV; it is restated here in numpy (monotone-chain hull + rotating calipers).
+"""
+import json
+
+import numpy as np
+
+
+def load_json(json_file):
+    if isinstance(json_file, dict):
+        return json_file
+    with open(json_file) as f:
+        return json.load(f)
+
+
+def _hull(pts):
+    """Convex hull (counter-clockwise, no collinear points) of [n, 2] float64 points."""
+    pts = np.unique(pts, axis=0)
+    if len(pts) < 3:
+        return pts
+    pts = pts[np.lexsort((pts[:, 1], pts[:, 0]))]
+
+    def cross(o, a, b):
+        return (a[0] - o[0]) * (b[1] - o[1]) - (a[1] - o[1]) * (b[0] - o[0])
+
+    lower, upper = [], []
+    for p in pts:
+        while len(lower) >= 2 and cross(lower[-2], lower[-1], p) <= 0:
+            lower.pop()
+        lower.append(p)
+    for p in pts[::-1]:
+        while len(upper) >= 2 and cross(upper[-2], upper[-1], p) <= 0:
+            upper.pop()
+        upper.append(p)
+    return np.array(lower[:-1] + upper[:-1])
+
+
+def min_area_rect_sides(pts):
+    """(w, h) of the minimum-area enclosing rectangle of [n, 2] points: one of its sides lies on a hull edge."""
+    hull = _hull(np.asarray(pts, np.float64).reshape(-1, 2))
+    if len(hull) < 3:
+        return None
+    best = None
+    for i in range(len(hull)):
+        e = hull[(i + 1) % len(hull)] - hull[i]
+        n = np.hypot(e[0], e[1])
+        if n == 0:
+            continue
+        u = e / n
+        v = np.array([-u[1], u[0]])
+        pu, pv = hull @ u, hull @ v
+        w, h = pu.max() - pu.min(), pv.max() - pv.min()
+        if best is None or w * h < best[0] * best[1]:
+            best = (w, h)
+    return best
+
+
+def _ratio_of_box(w, h):
+    if w * h == 0:
+        return 0.0
+    return min(w, h) / max(w, h)
+
+
+def polygon_ratio(polygons):
+    pts = np.concatenate([np.asarray(p, np.float64) for p in polygons]).reshape(-1, 2)
+    wh = min_area_rect_sides(pts)
+    if wh is None:       # fewer than 3 hull points: the axis-aligned extent
+        return _ratio_of_box(pts[:, 0].max() - pts[:, 0].min(), pts[:, 1].max() - pts[:, 1].min())
+    return _ratio_of_box(*wh)
+
+
+def gt_ratio(ann):
+    if "ratio" in ann:
+        return ann["ratio"]
+    seg = ann.get("segmentation")
+    polys = [p for p in seg if len(p) % 2 == 0 and len(p) >= 6] if isinstance(seg, list) else []
+    if ann["iscrowd"] or "segmentation" not in ann or len(polys) == 0:
+        w, h = ann["bbox"][2], ann["bbox"][3]
+        return min(w, h) / max(w, h)
+    return polygon_ratio(polys)
+
+
+class CocoGt:
+    """Index of a COCO-format dataset: sorted image and category ids, every annotation with its ratio, and the category maps."""
+
+    def __init__(self, dataset, id_map=None, class_names=None):
+        self.dataset = load_json(dataset)
+        self.img_ids = sorted({im["id"] for im in self.dataset.get("images", [])})
+        cats = self.dataset.get("categories", [])
+        self.cat_ids = sorted(c["id"] for c in cats)
+        self.cats = {c["id"]: c for c in cats}
+        # dataset category id -> contiguous id: the metadata's map, else the identity order over the sorted ids
+        self.id_map = dict(id_map) if id_map is not None else {c: i for i, c in enumerate(self.cat_ids)}
+        self.class_names = list(class_names) if class_names is not None else None
+        self.has_annotations = "annotations" in self.dataset
+        self.anns = list(self.dataset.get("annotations", []))
+        self.ratios = np.array([float(gt_ratio(a)) for a in self.anns], np.float64)
+        self._arrays = None
+
+    def arrays(self):
+        """Flat numpy arrays of the kernels' gt side (cached):
+        seg_gt_off [K*I+1] / seg_box [G,4] f64 / seg_crowd [G] u8 / seg_ratio [G] f64 - gts by (category, image) segment in json order;
+        img_gt_off [I+1] / img_box [G',4] f32 / img_cls [G'] i32 / img_ratio [G'] f32 - non-crowd gts by image for the recall pass."""
+        if self._arrays is not None:
+            return self._arrays
+        I, K = len(self.img_ids), len(self.cat_ids)
+        img_idx = {im: i for i, im in enumerate(self.img_ids)}
+        cat_idx = {c: k for k, c in enumerate(self.cat_ids)}
+        n = len(self.anns)
+        img_of = np.array([img_idx.get(a["image_id"], -1) for a in self.anns], np.int64)
+        cat_of = np.array([cat_idx.get(a["category_id"], -1) for a in self.anns], np.int64)
+        box = np.array([a["bbox"][:4] for a in self.anns], np.float64).reshape(n, 4)
+        crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in self.anns], np.uint8)
+        keep = (img_of >= 0) & (cat_of >= 0)
+        seg = cat_of * I + img_of
+        order = np.nonzero(keep)[0]
+        order = order[np.argsort(seg[order], kind="stable")]
+        seg_gt_off = np.zeros(K * I + 1, np.int32)
+        np.cumsum(np.bincount(seg[order], minlength=K * I), out=seg_gt_off[1:])
+        # recall pass: the non-crowd gts of each image, class mapped through the metadata map
+        ar_keep = np.nonzero((img_of >= 0) & (np.array([a["iscrowd"] == 0 for a in self.anns], bool) if n else np.zeros(0, bool)))[0]
+        ar_keep = ar_keep[np.argsort(img_of[ar_keep], kind="stable")]
+        img_gt_off = np.zeros(I + 1, np.int32)
+        np.cumsum(np.bincount(img_of[ar_keep], minlength=I), out=img_gt_off[1:])
+        img_cls = np.array([self.id_map[self.anns[j]["category_id"]] for j in ar_keep], np.int32)
+        self._arrays = dict(
+            seg_gt_off=seg_gt_off, seg_box=np.ascontiguousarray(box[order]), seg_crowd=crowd[order], seg_ratio=self.ratios[order],
+            img_gt_off=img_gt_off, img_box=box[ar_keep].astype(np.float32), img_cls=img_cls,
+            img_ratio=self.ratios[ar_keep].astype(np.float32),
+        )
+        return self._arrays
