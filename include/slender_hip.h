@@ -7,10 +7,13 @@
  *   - `stream` is a hipStream_t passed as void*; work is enqueued on it and the call returns without synchronising;
  *   - return value: 0 = ok, SOD_EARG (-1) bad argument / unsupported shape, SOD_ESIZE (-2) tensor exceeds the
  *     32-bit buffer addressing range (2 GiB per operand), >0 = hipError_t of a failed launch;
- *   - re-entrant per stream.  Process-wide state is limited to (a) one-time kernel attribute set-up and cached device properties
- *     (the library assumes every GPU of the process is the same model; one process per GPU is the supported deployment), (b) the
- *     tile-policy and experiment knobs read from SOD_* environment variables on first use and sod_conv_set_tile256, which select
- *     between kernels with identical contracts, and (c) the profiling aids sod_conv_prof_* (process-wide list) / sod_conv_last_variant (per thread).
+ *   - re-entrant per stream.  Process-wide state is limited to (a) the dynamic-LDS limit of each kernel, raised once behind an atomic
+ *     flag (safe to reach from several threads), and the cached compute-unit count (the library assumes every GPU of the process is the
+ *     same model; one process per GPU is the supported deployment), (b) the one table of convolution dispatch knobs, which select between
+ *     kernels with identical contracts: SOD_CONV256 / SOD_CONV_PW / SOD_CONV_WS3 are read at the first dispatch and again after their
+ *     setter (sod_conv_set_tile256 / _pw / _ws3) was given -1, SOD_WGRAD256 / SOD_WGRAD9 / SOD_WGRAD9_MIN_KT are read once,
+ *     sod_conv_set_wgrad_variant has no variable; the setters are not synchronised with launches on other threads (sod_conv_set_reverse
+ *     is per calling thread), and (c) the profiling aids sod_conv_prof_* (process-wide list) / sod_conv_last_variant (per thread).
  *     Scratch memory is never cached inside the library: every entry point that needs a workspace takes it as an argument.
  *
  * Each declaration cites the reference interface it replaces (paths under wanzysky/SlenderObjDet; "d2" =

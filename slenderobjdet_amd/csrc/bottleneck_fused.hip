@@ -331,16 +331,10 @@ template <int NK, bool PROJ>
 int launch_bneck(const BneckArgs& a, hipStream_t st) {
   constexpr int NR = (NK == 1) ? 2 : NK;
   constexpr int lds = NR * SLOT + SLOT + 128 * BT_ROWB + 4 * 16 * EROWB;
-  auto kern = bottleneck_frozen_kernel<NK, PROJ>;
-  static bool attr_done = false;
-  static int cus = 0;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-    attr_done = true;
-  }
+  constexpr auto kern = bottleneck_frozen_kernel<NK, PROJ>;
+  const hipError_t e = sod_max_dynamic_lds_once<kern>(lds);
+  if (e != hipSuccess) return (int)e;
+  const int cus = device_cus();
   const long long ntiles = (long long)a.N * a.tiles_x * a.tiles_y;
   const unsigned grid = (unsigned)(ntiles < cus ? ntiles : cus);
   SOD_LAUNCH(kern, dim3(grid), dim3(256), lds, st, a);

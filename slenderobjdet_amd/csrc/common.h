@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <atomic>
 
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8_t;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4_t;
@@ -80,3 +81,18 @@ __device__ __forceinline__ void sod_store16(void* p, V v) {
 
 // Launch + error attribution: clear any stale (sticky-less) error left by other HIP users in this thread first.
 #define SOD_LAUNCH(...) do { (void)hipGetLastError(); hipLaunchKernelGGL(__VA_ARGS__); } while (0)
+
+// Raises a kernel's dynamic-LDS limit to `bytes`, once per kernel symbol and process: every later call is one load.  Callable from
+// several threads (the forward thread and autograd's worker both launch convolutions): two first calls that race both set the same value.
+// A failed call is returned and tried again at the next launch.
+template <auto KERN>
+inline hipError_t sod_max_dynamic_lds_once(int bytes) {
+  static std::atomic<bool> done{false};
+  if (done.load(std::memory_order_acquire)) return hipSuccess;
+  const hipError_t e = hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, bytes);
+  if (e == hipSuccess) done.store(true, std::memory_order_release);
+  return e;
+}
+
+// Compute units of the current device, queried once per process (256 if the query fails); conv_dispatch.hip.
+int device_cus();

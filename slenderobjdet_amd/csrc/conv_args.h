@@ -1,4 +1,5 @@
-// Argument blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm256.hip).
+// Argument blocks shared by the implicit-GEMM convolution kernels (conv_igemm.hip, conv_igemm256.hip, ...), and their launchers as
+// conv_dispatch.hip calls them.
 #pragma once
 #include "common.h"
 #include "../../include/slender_hip.h"
@@ -106,6 +107,12 @@ __device__ __forceinline__ void gn_acc_finish(GnAcc& g, uint32_t pa, uint32_t pb
   }
 }
 
+// conv_igemm.hip: the 128x128-family kernel.  Tile = BQ output channels x BP pixels per workgroup, 64 contraction elements per K-step
+// (_K32: 32, linear path only); `generic` = the per-chunk gather path for channel counts that are no multiple of 64.  *variant receives
+// BQ * 100000 + BP * 100 + BK + generic (sod_conv_last_variant).
+enum ConvTile { TILE_16x256, TILE_64x256, TILE_64x256_K32, TILE_128x128, TILE_128x128_K32 };
+int launch_conv128(const ConvArgs& a, int mode, bool out_f32, ConvTile tile, bool generic, hipStream_t st, int* variant);
+
 // conv_igemm256.hip: 256x256x64 tile, 8 waves, 8-phase main loop.  Returns SOD_EARG when the shape is outside its fast path.
 bool conv256_supported(const ConvArgs& a, int mode);
 // max_pt_tiles > 0 launches only the first max_pt_tiles pixel tiles (the caller covers the rest with the 128x128 kernel).
@@ -123,7 +130,7 @@ int launch_ws3(const ConvArgs& a, int mode, hipStream_t st);
 // --------------------------------------------------------------------------------------------
 // wgrad: dW[q][tap][c] += sum_p dY[p][q] * X[p shifted by tap][c]
 // The contraction runs over a VIRTUAL pixel index that concatenates the levels (each padded to a multiple of 64), so
-// one launch reduces over all FPN levels that share the weights.  (conv_igemm.hip: 128x128 tiles; conv_wgrad256.hip: 256x256.)
+// one launch reduces over all FPN levels that share the weights.  (conv_igemm.hip: 128x128 tiles; conv_wgrad256.hip: 256x256; conv_dispatch.hip chooses.)
 // --------------------------------------------------------------------------------------------
 struct WLevel {
   const void* dy;      // (N,Ho,Wo,K) bf16 rows at dy_img_stride
@@ -152,6 +159,12 @@ struct WgradArgs {
 };
 
 enum { WGRAD_DETERMINISTIC = 1, WGRAD_DIAG = 2 };   // sod_conv2d_wgrad flags
+
+// conv_igemm.hip: 128 x 128 tile, pixel splits that meet in dw with float atomics or (a.det) in slabs of `ws` summed by wgrad_reduce_kernel.
+// The caller fills a.QT / a.CT / a.V and the levels' v0; splits <= 0 = one resident wave of workgroups.
+int launch_wgrad128(WgradArgs& a, int cus, int splits, float* ws, long long ws_bytes, hipStream_t st);
+// wgrad_reduce_kernel alone: sums the a.nz slabs per tile that launch_wgrad_ring left in a.partial
+int launch_wgrad_reduce(const WgradArgs& a, hipStream_t st);
 
 // conv_wgrad256.hip: 256(q) x 256(c) output tile per workgroup of 8 waves, one workgroup per CU, split over pixels with fp32 slabs in
 // the caller's workspace and a fixed-order reduce kernel (no atomics anywhere).

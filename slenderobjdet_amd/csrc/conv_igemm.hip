@@ -13,48 +13,14 @@
 //
 // wgrad contracts over pixels, which is the slow axis of both operands: tiles are staged [pixel][128 ch]
 // and fragments are fetched with ds_read_b64_tr_b16 (hardware transpose), swizzled at 32-B granularity.
+//
+// Kernels and their plain launchers only: which shapes come here (and with which tile) is decided in conv_dispatch.hip.
 #include "conv_args.h"
-#include <stdlib.h>
 #include <type_traits>
-#include <atomic>
-#include <algorithm>
 
 using namespace sodconv;
 
 namespace {
-
-thread_local int g_last_variant = 0;   // kernel variant chosen by the last forward / data-gradient dispatch (sod_conv_last_variant)
-
-// Optional in-library timing of the conv launches (sod_conv_prof_enable / _collect): one hipEvent pair per top-level dispatch,
-// recorded on the launch stream right around the MAIN kernel (for a split dispatch the 256x256 launch; `frac` is its share of the
-// output pixels), so that the durations are comparable with rocprofv3's per-kernel figures.  The list is process-wide: autograd runs
-// the backward pass on its own thread, and its dispatches belong to the same step as the forward ones.  Slots are reserved with an
-// atomic counter; the nesting depth (tail launches of a split dispatch) is a per-thread property.
-struct ConvProf {
-  hipEvent_t* ev = nullptr;
-  int* variant = nullptr;
-  int* mode = nullptr;
-  float* frac = nullptr;
-  int cap = 0;
-  std::atomic<int> n{0};
-  std::atomic<int> on{0};
-};
-ConvProf g_prof;
-thread_local int g_prof_depth = 0;
-inline int prof_begin(hipStream_t st) {
-  ConvProf& p = g_prof;
-  if (!p.on.load(std::memory_order_relaxed) || g_prof_depth) return -1;
-  const int i = p.n.fetch_add(1);
-  if (i >= p.cap) { p.n.store(p.cap); return -1; }
-  (void)hipEventRecord(p.ev[2 * i], st);
-  return i;
-}
-inline void prof_end(int i, hipStream_t st, int variant, float frac, int mode) {
-  if (i < 0) return;
-  ConvProf& p = g_prof;
-  (void)hipEventRecord(p.ev[2 * i + 1], st);
-  p.variant[i] = variant; p.frac[i] = frac; p.mode[i] = mode;
-}
 
 template <int MODE, bool GENERIC, int WQ, int WP, int FQ, int FP, bool OUT_F32, int BK, int NSTAGE>
 __global__ __launch_bounds__(64 * WQ * WP, (WQ * WP == 4 && BK == 32 && NSTAGE == 2) ? 4 : 2) void conv_igemm_kernel(const ConvArgs a) {
@@ -840,7 +806,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const WgradArgs a) {
 }
 
 template <int MODE, bool GENERIC, int WQ, int WP, int FQ, int FP, bool OUT_F32, int BK = 64, int NSTAGE = 2>
-int launch_conv(const ConvArgs& a0, hipStream_t st) {
+int launch_conv(const ConvArgs& a0, hipStream_t st, int* variant) {
   constexpr int BQ = WQ * FQ * 16, BP = WP * FP * 16;
   ConvArgs a = a0;
   a.T = (a.Kred + BK - 1) / BK;
@@ -866,323 +832,44 @@ int launch_conv(const ConvArgs& a0, hipStream_t st) {
   const size_t epi = (size_t)(WQ * WP) * (size_t)(FP / 2) * 16 * (FQ * 64 + 16);
   size_t lds = a.T == 1 ? (size_t)(BQ + BP) * BK * 2 : lds_full;
   if (lds < epi) lds = epi;
-  g_last_variant = BQ * 100000 + BP * 100 + BK + (GENERIC ? 1 : 0);
-  auto kern = conv_igemm_kernel<MODE, GENERIC, WQ, WP, FQ, FP, OUT_F32, BK, NSTAGE>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds_full > epi ? lds_full : epi));
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
-  const int pi = prof_begin(st);
+  *variant = BQ * 100000 + BP * 100 + BK + (GENERIC ? 1 : 0);
+  constexpr auto kern = conv_igemm_kernel<MODE, GENERIC, WQ, WP, FQ, FP, OUT_F32, BK, NSTAGE>;
+  const hipError_t e = sod_max_dynamic_lds_once<kern>((int)(lds_full > epi ? lds_full : epi));
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(kern, dim3(a.nq_tiles * a.np_tiles), dim3(64 * WQ * WP), lds, st, a);
-  prof_end(pi, st, g_last_variant, 1.f, MODE);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
 
-thread_local int g_conv_reverse = 0;    // sod_conv_set_reverse: per calling thread (the forward thread and autograd's worker each bracket their own launches)
-int g_conv256_mode = -1;   // -1: read SOD_CONV256 (default 1); 0 off; 1 heuristic; 2 every supported shape
-int g_conv_pw = -1;        // -1: read SOD_CONV_PW (default 1); 0 off; 1 on (sod_conv_set_pw)
-int g_conv_ws3 = -1;       // -1: read SOD_CONV_WS3 (default 1); 0 off; 1 large launches; 2 every supported shape (sod_conv_set_ws3)
-int device_cus();
-
 template <int MODE, bool OUT_F32>
-int dispatch_conv(const ConvArgs& a, hipStream_t st) {
-  const bool generic = (a.Cred & 63) != 0 || a.R * a.S > 64;      // the linear path keeps one validity bit per tap in 64-bit masks
-  if (a.cwin) {         // channel window: the window IS the 128-row q-tile of this variant; Cred = 128 -> never generic
-    if (generic || a.nlev != 1 || (a.Nout & 127)) return SOD_EARG;
-    return launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32>(a, st);
+int launch_tile(const ConvArgs& a, ConvTile tile, bool generic, hipStream_t st, int* variant) {
+  switch (tile) {
+    case TILE_16x256:
+      return generic ? launch_conv<MODE, true, 1, 4, 1, 4, OUT_F32>(a, st, variant) : launch_conv<MODE, false, 1, 4, 1, 4, OUT_F32>(a, st, variant);
+    case TILE_64x256:
+      return generic ? launch_conv<MODE, true, 1, 4, 4, 4, OUT_F32>(a, st, variant) : launch_conv<MODE, false, 1, 4, 4, 4, OUT_F32>(a, st, variant);
+    case TILE_128x128:
+      return generic ? launch_conv<MODE, true, 2, 2, 4, 4, OUT_F32>(a, st, variant) : launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32>(a, st, variant);
+    case TILE_64x256_K32:
+      return generic ? SOD_EARG : launch_conv<MODE, false, 1, 4, 4, 4, OUT_F32, 32>(a, st, variant);
+    case TILE_128x128_K32:
+      return generic ? SOD_EARG : launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32, 32>(a, st, variant);
   }
-  // persistent weight-stationary kernel (conv_pw.hip) for the expanding 1x1 convolutions; SOD_CONV_PW=0 / sod_conv_set_pw(0) disables it
-  if (g_conv_pw < 0) { const char* e = getenv("SOD_CONV_PW"); g_conv_pw = e ? atoi(e) : 1; }
-  if (g_conv_pw && pw_supported(a, MODE, OUT_F32, device_cus())) {
-    g_last_variant = 7001;
-    const int pi = prof_begin(st);
-    const int rc = launch_pw(a, MODE, st);
-    prof_end(pi, st, 7001, 1.f, MODE);
-    return rc;
-  }
-  // persistent weight-stationary 3x3 kernel (conv_ws3.hip) for the 128 -> 128 convolutions of res3; SOD_CONV_WS3=0 disables it
-  if (g_conv_ws3 < 0) { const char* e = getenv("SOD_CONV_WS3"); g_conv_ws3 = e ? atoi(e) : 1; }
-  if (g_conv_ws3 && ws3_supported(a, MODE, OUT_F32, device_cus(), g_conv_ws3 == 2)) {
-    g_last_variant = 7003;
-    const int pi = prof_begin(st);
-    const int rc = launch_ws3(a, MODE, st);
-    prof_end(pi, st, 7003, 1.f, MODE);
-    return rc;
-  }
-  // 256x256 8-phase kernel (conv_igemm256.hip) for the large compute-bound shapes.  SOD_CONV256=0 disables it, =2 forces it for
-  // every shape it supports (parity tests).
-  static int cus = 0;
-  int& c256 = g_conv256_mode;
-  if (c256 < 0 || cus == 0) {
-    if (c256 < 0) { const char* e = getenv("SOD_CONV256"); c256 = e ? atoi(e) : 1; }
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  bool any_start = false;
-  for (int l = 0; l < a.nlev; ++l) any_start |= a.lev[l].pstart != 0;
-  // Data gradients use the 256 kernel as well.  Beside the wgrad side stream the answer depends on what the wgrad blocks leave free:
-  // with 3-4 small wgrad workgroups per CU the 128-KB workgroup rarely found a CU (490 vs 487.5 img/s in favour of 128x128); with two
-  // ring workgroups per CU and the faster wgrad it wins 542.4 vs 536.0.
-  if (c256 && !any_start && !(a.flags & (F_WBITS | F_MASKBITS)) && conv256_supported(a, MODE)) {
-    const int nq = (a.Nout + 255) / 256;
-    long long pt256 = 0;
-    for (int l = 0; l < a.nlev; ++l) pt256 += (a.lev[l].P + 255) / 256;
-    const long long b256 = pt256 * nq;
-    if (c256 == 2) {
-      g_last_variant = 256;
-      const int pi = prof_begin(st);
-      const int rc = launch_conv256(a, MODE, OUT_F32, 0, st);
-      prof_end(pi, st, 256, 1.f, MODE);
-      return rc;
-    }
-    // (thresholds swept in rounds 2 - 4, DESIGN.md section 4: contraction >= 1024 - 512 / 256 measured 587-588 / 575 vs 593 img/s -, at
-    // least one full round of tiles, output-channel counts that are no multiple of 256 - RetinaNet's 720 class scores: the third q-tile
-    // is 19 % empty - from 512 channels up)
-    constexpr int min_rounds = 1, min_k = 1024;
-    if (a.Nout >= 256 && ((a.Nout & 255) == 0 || a.Nout >= 512) && a.Kred >= min_k && b256 >= (long long)min_rounds * cus) {
-      // Measured (16 x FPN levels, 256 -> 256 3x3): 1020-1040 TFLOP/s against 840-930 for the 128x128 kernel.  Shapes with barely more
-      // than one round of tiles (res4 conv2: 263 tiles = one round + a 7-tile remainder launch) measured slower stand-alone but win in
-      // the training step (545.8-546.3 vs 541.2-542.9 img/s), so one full round is enough.
-      // One workgroup per CU: a partial last round of 256x256 tiles wastes up to a whole round.  Whole rounds go to the 256 kernel,
-      // a remainder below half a round is computed by the 128x128 kernel (two workgroups per CU, 4x smaller tiles) instead
-      // (P3 output conv, 4.1 rounds: 1035 -> 1075 TFLOP/s).  Round 5 re-measured the threshold on the step - remainders up to 50 / 30 /
-      // 12 / 5 % of a round split off: 633.2 / 631.7 / 634.6 / 631.0 img/s, three alternating 100-step runs each - no difference.
-      const long long full = b256 / cus * cus, rem = b256 - full;
-      if (rem == 0 || rem * 2 >= (long long)cus || (full / nq) * nq != full) {
-        g_last_variant = 256;
-        const int pi = prof_begin(st);
-        const int rc = launch_conv256(a, MODE, OUT_F32, 0, st);
-        prof_end(pi, st, 256, 1.f, MODE);
-        return rc;
-      }
-      int main_pt = (int)(full / nq);
-      long long ptot = 0;
-      for (int l = 0; l < a.nlev; ++l) ptot += a.lev[l].P;
-      const int pi = prof_begin(st);
-      int rc = launch_conv256(a, MODE, OUT_F32, main_pt, st);
-      prof_end(pi, st, 256, (float)((double)main_pt * 256.0 / (double)ptot), MODE);     // main tiles are full 256-pixel tiles
-      if (rc) return rc;
-      ConvArgs tail = a;
-      for (int l = 0; l < tail.nlev; ++l) {
-        const int tl = (tail.lev[l].P + 255) / 256;
-        if (main_pt >= tl) { tail.lev[l].pstart = tail.lev[l].P; main_pt -= tl; }
-        else { tail.lev[l].pstart = main_pt * 256; main_pt = 0; }
-      }
-      ++g_prof_depth;            // the tail launch belongs to this dispatch: no event pair of its own
-      rc = dispatch_conv<MODE, OUT_F32>(tail, st);
-      --g_prof_depth;
-      g_last_variant = 256;      // whole rounds on the 256 kernel (+ a short 128x128 tail launch)
-      return rc;
-    }
-  }
-  // (Round 6 measured an 80(q) x 256(p) tile - one wave row of 5 x 4 MFMA blocks, BK = 32, three workgroups per CU - for the 80 class scores
-  // instead of 128 x 128 with 37.5 % of the q-tile empty: 195-204 us against 170 us on the P3 level, 664.1 vs 665.4 img/s on the step.  These
-  // convolutions are bound by the pixel operand's way into LDS, not by the matrix pipe; not kept.)
-  if (a.Nout <= 16) {
-    return generic ? launch_conv<MODE, true, 1, 4, 1, 4, OUT_F32>(a, st) : launch_conv<MODE, false, 1, 4, 1, 4, OUT_F32>(a, st);
-  } else if (a.Nout <= 64) {
-    // BK = 32: 4 blocks per CU for the res2-sized convs, +0.3 % on the step
-    if (!generic && (a.Cred & 31) == 0) return launch_conv<MODE, false, 1, 4, 4, 4, OUT_F32, 32>(a, st);
-    return generic ? launch_conv<MODE, true, 1, 4, 4, 4, OUT_F32>(a, st) : launch_conv<MODE, false, 1, 4, 4, 4, OUT_F32>(a, st);
-  }
-  // BK = 32 halves the LDS footprint (4 resident blocks per CU instead of 2): measured better for the latency-/write-bound
-  // cases - short contractions - and worse for the large compute-bound shapes (head 3x3: 820 vs 699 TFLOP/s).
-  long long blocks = 0;
-  for (int l = 0; l < a.nlev; ++l) blocks += (a.lev[l].P - a.lev[l].pstart + 127) / 128;
-  blocks *= (a.Nout + 127) / 128;
-  // Re-measured per shape after the epilogue fix (serial run, best of the two variants 19.4 vs 19.9 ms of conv per step): grids that fit
-  // one round of two blocks per CU want BK = 64 (P5/P6 3x3: 44 vs 54 us); otherwise BK = 32 also wins for Kred <= 512 (the 512-channel
-  // 1x1 convs: 276 vs 300 us) and for the 128-channel 3x3 convs.
-  const bool use32 = !generic && (a.Cred & 31) == 0 && blocks > 512 &&
-                     (a.Kred <= 512 || blocks <= 1024 || (a.Cred <= 128 && a.Kred <= 1152));
-  // (Measured and removed in round 5: a 3 / 4 / 5-slot LDS ring for the 32-deep K-steps - 113 -> 117 / 114 / 114 us on res3 conv3, -30 %
-  // where it halves the workgroups per CU - and a 128(q) x 256(p) 8-wave tile with a 3-slot ring, 717 vs 813 TFLOP/s on the head shape;
-  // a 4-slot ring of 64-deep steps for the one-workgroup-per-CU grids of the FPN top (P6 / P7, 20 - 70 workgroups): 29.4 vs 28.1 us -
-  // their 0.78 us per K-step is issue time of one wave per SIMD, not load latency.)
-  if (use32) return launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32, 32>(a, st);
-  return generic ? launch_conv<MODE, true, 2, 2, 4, 4, OUT_F32>(a, st) : launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32>(a, st);
+  return SOD_EARG;
 }
 
-int out_size(int H, int pad, int dil, int R, int stride) { return (H + 2 * pad - dil * (R - 1) - 1) / stride + 1; }
+}  // namespace
 
-int fill_common(ConvArgs& a, int nlev, int N, int Cred, int Nout, int R, int S, int stride, int pad, int dil) {
-  if (nlev <= 0 || nlev > MAXLEV) return SOD_EARG;
-  if (N <= 0 || Nout <= 0 || R <= 0 || S <= 0 || stride <= 0 || dil <= 0 || pad < 0) return SOD_EARG;
-  if (Cred <= 0 || (Cred & 7)) return SOD_EARG;
-  const unsigned long long wb = (unsigned long long)Nout * R * S * Cred * 2ull;
-  if (wb >= 0x80000000ull) return SOD_ESIZE;
-  a.nlev = nlev;
-  a.w_bytes = (uint32_t)wb;
-  a.N = N; a.Cred = Cred; a.Nout = Nout; a.Cpitch = Cred; a.cwin = 0;
-  a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.dil = dil;
-  a.Kred = R * S * Cred; a.T = (a.Kred + 63) / 64;
-  a.div_cpt = make_fastdiv((uint32_t)((Cred & 63) ? Cred / 8 : Cred / 64));
-  a.div_s = make_fastdiv((uint32_t)S);
-  a.div_stride = make_fastdiv((uint32_t)stride);
-  return SOD_OK;
+namespace sodconv {
+
+int launch_conv128(const ConvArgs& a, int mode, bool out_f32, ConvTile tile, bool generic, hipStream_t st, int* variant) {
+  if (mode == MODE_FWD) return out_f32 ? launch_tile<MODE_FWD, true>(a, tile, generic, st, variant) : launch_tile<MODE_FWD, false>(a, tile, generic, st, variant);
+  if (out_f32) return SOD_EARG;      // data gradients are bf16
+  return launch_tile<MODE_DGRAD, false>(a, tile, generic, st, variant);
 }
 
-// source dims (Hs,Ws) with Cred channels; GEMM-row dims (Hp,Wp) with Nout channels
-int fill_level(ConvArgs& a, int l, const void* src, void* dst, int Hs, int Ws, int Hp, int Wp, long long src_img_stride,
-               long long dst_img_stride, size_t dst_elt) {
-  if (!src || !dst || Hs <= 0 || Ws <= 0 || Hp <= 0 || Wp <= 0) return SOD_EARG;
-  if (src_img_stride <= 0) src_img_stride = (long long)Hs * Ws * a.Cpitch;
-  if (dst_img_stride <= 0) dst_img_stride = (long long)Hp * Wp * a.Nout;
-  if (src_img_stride < (long long)Hs * Ws * a.Cpitch || dst_img_stride < (long long)Hp * Wp * a.Nout) return SOD_EARG;
-  const unsigned long long sb = (unsigned long long)a.N * src_img_stride * 2ull;
-  const unsigned long long db = (unsigned long long)a.N * dst_img_stride * dst_elt;
-  if (sb >= 0x80000000ull || db >= 0x200000000ull) return SOD_ESIZE;
-  if ((long long)a.N * Hp * Wp >= (1ll << 31)) return SOD_ESIZE;
-  LevelGeo& g = a.lev[l];
-  g.src = src; g.dst = dst; g.res = nullptr; g.mask = nullptr; g.pstart = 0;
-  g.src_bytes = (uint32_t)sb;
-  g.Hs = Hs; g.Ws = Ws; g.Hp = Hp; g.Wp = Wp; g.P = a.N * Hp * Wp;
-  g.src_img_stride = (int)src_img_stride; g.dst_img_stride = (int)dst_img_stride; g.res_img_stride = 0;
-  g.div_hw = make_fastdiv((uint32_t)(Hp * Wp));
-  g.div_w = make_fastdiv((uint32_t)Wp);
-  return SOD_OK;
-}
-
-int device_cus() {
-  static int cus = 0;
-  if (!cus) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  }
-  return cus;
-}
-
-// Which kernel a weight gradient goes to.  SOD_WGRAD256: 0 = never, 1 (default) = shapes with K, C multiples of 256 whose blocks get
-// at least 64 K-tiles of work each, 2 = every supported shape (parity tests).
-bool use_wgrad256(const WgradArgs& a, float* ws, long long ws_bytes) {
-  static const int mode = getenv("SOD_WGRAD256") ? atoi(getenv("SOD_WGRAD256")) : 1;
-  // Blocks with few K-tiles are dominated by their 256-KB slab write, and the 48-KB workgroups of the 128x128 kernel share CUs with the
-  // data-gradient kernels on the other stream.  Swept on the FCOS R50 step (one box, two rounds): >= 6 K-tiles per block 572.1 / 573.5
-  // img/s, >= 40: 575.5 / 576.5, >= 70: 576.7 / 577.4, >= 120: 576.6 / 577.2, >= 250 (head towers off the 256 kernel): 565.6 / 566.1.
-  // (re-swept with the faster kernel in round 4: 64 still best - 635.6 / 634.3 vs 633.2 at 32, 627-628 at 16 / 8)
-  // (round 6, with the nine-tap kernel taking the long 3x3 shapes and the head's weight gradients parked behind the FPN backward: 32 beats 64 -
-  // 663.9 / 662.5 / 664.6 vs 662.1 / 659.8 / 660.3 img/s, 20: 662.8 / 662.0 / 662.4; stand-alone the 256 kernel wins from ~30 K-tiles per block)
-  constexpr int min_kt = 32;
-  if (!mode || !ws || !wgrad256_supported(a)) return false;
-  const int cus = device_cus();
-  if (wgrad256_workspace_bytes(a, cus) > ws_bytes) return false;
-  if (mode == 2) return true;
-  // The kernel masks a partial last q-tile (K = 720 of RetinaNet's class scores: 27 tiles of which 9 are 19 % empty).  Until round 4 that
-  // shape measured slower on it than on the 128x128 kernel (RetinaNet R50 527.5 / 527.1 vs 533.0 / 531.2 img/s); with the row arithmetic
-  // out of the K loop it wins (546.6 / 548.5 vs 542.1 / 540.4; the 128x128 launch took 2.6 ms).
-  long long V = 0;
-  for (int l = 0; l < a.nlev; ++l) V += (a.lev[l].P + 63) / 64 * 64;
-  const long long tiles = (long long)((a.K + 255) / 256) * (a.C / 256) * a.R * a.S;
-  const long long nz = cus / tiles > 0 ? cus / tiles : 1;
-  return V / 64 >= nz * min_kt;
-}
-
-// The nine-tap kernel (conv_wgrad9.hip) for the 3x3 convolutions it supports.  SOD_WGRAD9: 0 = never, 1 (default) = when every block gets
-// at least `min_kt` K-tiles (prologue: ~E + 3 tile loads per level, epilogue: a 288-KB slab), 2 = every supported shape (parity tests).
-bool use_wgrad9(const WgradArgs& a, float* ws, long long ws_bytes) {
-  static const int mode = getenv("SOD_WGRAD9") ? atoi(getenv("SOD_WGRAD9")) : 1;
-  static const int min_kt = getenv("SOD_WGRAD9_MIN_KT") ? atoi(getenv("SOD_WGRAD9_MIN_KT")) : 24;
-  if (!mode || !ws || !wgrad9_supported(a)) return false;
-  const int cus = device_cus();
-  if (wgrad9_workspace_bytes(a, cus) > ws_bytes) return false;
-  return mode == 2 || wgrad9_tiles_per_block(a, cus) >= min_kt;
-}
-
-int g_wgrad_variant = -1;    // sod_conv_set_wgrad_variant
-
-// Which variant of conv_wgrad_ring.hip a weight gradient takes (0 = conv_wgrad_kernel below).
-int ring_variant_for(const WgradArgs& a, int tiles, int splits, float* ws, long long ws_bytes) {
-  const int v = g_wgrad_variant;
-  if (a.diag) return 0;          // grouped convolutions: conv_wgrad_kernel's diagonal-tile mode only
-  if (v >= 0) return v;
-  // Measured per shape (tools/bench_wgrad_backbone.py, FCOS R50 at batch 16): the two groups of a workgroup halve the atomic bytes
-  // (16 instead of 32 MB per launch: -9 ... -15 us on the 1x1 shapes of res3 / res4 / res5) but share one barrier per K-step, which costs
-  // 3 - 9 % in long loops; the gain outweighs that up to ~100 K-steps per group.  Explicit split counts (tests) and deterministic mode
-  // keep conv_wgrad_kernel and its slab reduce.
-  if (splits != 0 || a.det || a.diag || tiles > 128) return 0;
-  const int cus = device_cus();
-  const long long steps = (long long)a.V / std::max(1, 2 * cus / tiles) / 32;
-  return steps <= 100 ? 2300 : 0;
-}
-
-int launch_wgrad(WgradArgs& a, int splits, int flags, hipStream_t st, float* ws = nullptr, long long ws_bytes = 0) {
-  a.det = (flags & WGRAD_DETERMINISTIC) ? 1 : 0;
-  a.diag = (flags & WGRAD_DIAG) ? 1 : 0;
-  if (a.diag && (a.C != a.K || (a.C & 127) || splits < 0)) return SOD_EARG;
-  // splits == -2 forces the nine-tap kernel, -1 the 256 x 256 kernel (tests, tools); 0 = the dispatcher's choice
-  if (splits == -2 && (!ws || !wgrad9_supported(a) || wgrad9_workspace_bytes(a, device_cus()) > ws_bytes)) return SOD_EARG;
-  if (splits == -2 || (splits == 0 && use_wgrad9(a, ws, ws_bytes))) {
-    const int pi = prof_begin(st);
-    const int rc = launch_wgrad9(a, device_cus(), ws, ws_bytes, st);
-    prof_end(pi, st, 9009, 1.f, 2);
-    return rc;
-  }
-  if (splits == -1 && (!ws || !wgrad256_supported(a) || wgrad256_workspace_bytes(a, device_cus()) > ws_bytes)) return SOD_EARG;
-  if (splits == -1 || (splits == 0 && !a.diag && use_wgrad256(a, ws, ws_bytes))) {
-    const int pi = prof_begin(st);
-    const int rc = launch_wgrad256(a, device_cus(), ws, ws_bytes, st);
-    prof_end(pi, st, 256, 1.f, 2);
-    return rc;
-  }
-  // few output channels (prediction convolutions): the taps folded into the tile rows, conv_wgrad_fold.hip
-  if (splits == 0 && wgrad_fold_supported(a)) {
-    const int pi = prof_begin(st);
-    const int rc = launch_wgrad_fold(a, device_cus(), st);
-    prof_end(pi, st, 32004, 1.f, 2);
-    return rc;
-  }
-  a.QT = (a.K + 127) / 128; a.CT = a.diag ? 1 : (a.C + 127) / 128;
+int launch_wgrad128(WgradArgs& a, int cus, int splits, float* ws, long long ws_bytes, hipStream_t st) {
   const int tiles = a.QT * a.CT * a.R * a.S;
-  int V = 0;
-  long long Ptot = 0;
-  for (int l = 0; l < a.nlev; ++l) {
-    a.lev[l].v0 = V;
-    V += (a.lev[l].P + 63) / 64 * 64;
-    Ptot += a.lev[l].P;
-  }
-  a.V = V;
-  // In-workgroup split over pixels with an LDS combine (conv_wgrad_ring.hip).  g_wgrad_variant: 0 = the kernel below, > 0 forces one
-  // variant of launch_wgrad_ring for every shape, -1 (default) = the per-shape choice of ring_variant_for().
-  {
-    const int variant = ring_variant_for(a, tiles, splits, ws, ws_bytes);
-    if (variant > 0) {
-      const int cus = device_cus();
-      const int G = (variant % 10000) / 1000;      // + 10000 * ABL in ablation builds (conv_wgrad_ring.hip)
-      int epi = (variant / 10) % 10;
-      long long total = splits > 0 ? splits : (long long)G * std::max(1, (G == 1 ? 2 : 1) * cus / tiles);
-      const long long maxs = (Ptot + 255) / 256;
-      if (total > maxs) total = maxs;
-      if (total < 1) total = 1;
-      int vps = (int)((V + total - 1) / total);
-      vps = (vps + 63) / 64 * 64;
-      const int nsplit = (V + vps - 1) / vps;
-      a.v_per_split = vps;
-      a.nz = (nsplit + G - 1) / G;
-      a.dbg_plain_store = 0;
-      const long long need = (long long)a.nz * tiles * 128 * 128 * (long long)sizeof(float);
-      if (a.det || epi == 1) {
-        if (!ws || need > ws_bytes) {
-          if (a.det) return SOD_EARG;
-          epi = 0;
-        }
-      }
-      a.partial = (a.det || epi == 1) ? ws : nullptr;
-      const int v = variant - ((variant / 10) % 10) * 10 + (a.partial ? 10 : 0);
-      const int pi = prof_begin(st);
-      const int rc = launch_wgrad_ring(a, v, st);
-      if (rc) return rc;
-      if (a.partial) {
-        const int gx = (tiles * 128 * 32 + 255) / 256;
-        SOD_LAUNCH(wgrad_reduce_kernel, dim3(gx, 1), dim3(256), 0, st, a);
-      }
-      prof_end(pi, st, v % 10000, 1.f, 2);          // G*1000 + NSTAGE*100 + EPI*10 + FDB (bench.py: kernel_name)
-      SOD_CHECK_LAUNCH();
-      return SOD_OK;
-    }
-  }
   // 32 pixels per K-step, three-slot LDS ring (48 KB, 131 VGPRs) for every shape.  In the training step the wgrad kernels run on the side
   // stream BESIDE the data-gradient kernels, so the LDS footprint counts as well as the stand-alone rate.  Last sweeps on the FCOS R50 step
   // (rounds 1 - 2): ring everywhere, 2 workgroups per CU 581.2 / 581.0 img/s, 3 per CU 576.1 / 575.2, 1: 564; 64-pixel steps with two
@@ -1190,16 +877,17 @@ int launch_wgrad(WgradArgs& a, int splits, int flags, hipStream_t st, float* ws 
   if (splits <= 0) {
     // ONE resident wave of blocks (2 per CU): measured on the head shape, 504 blocks run at 718 TFLOP/s where 1548 blocks
     // (3.02 waves -> a nearly empty 4th round, 3x the atomic traffic) run at 585.  At least 256 pixels per block.
-    const int cus = device_cus();
+    long long Ptot = 0;
+    for (int l = 0; l < a.nlev; ++l) Ptot += a.lev[l].P;
     splits = 2 * cus / tiles;
     const int maxs = (int)((Ptot + 255) / 256);
     if (splits > maxs) splits = maxs;
     if (splits < 1) splits = 1;
   }
-  int vps = (V + splits - 1) / splits;
+  int vps = (a.V + splits - 1) / splits;
   vps = (vps + 63) / 64 * 64;
   a.v_per_split = vps;
-  a.nz = (V + vps - 1) / vps;
+  a.nz = (a.V + vps - 1) / vps;
   a.div_s = make_fastdiv((uint32_t)a.S);
   a.dbg_plain_store = 0;
   // Deterministic mode: fp32 partial tiles in the workspace + wgrad_reduce_kernel, summed in a fixed order with plain read-modify-writes;
@@ -1211,7 +899,6 @@ int launch_wgrad(WgradArgs& a, int splits, int flags, hipStream_t st, float* ws 
   } else {
     a.partial = nullptr;
   }
-  const int pi = prof_begin(st);
   SOD_LAUNCH((conv_wgrad_kernel<32, 3>), dim3(a.nz * tiles), dim3(256), 3 * 2 * 32 * 256, st, a);
   if (a.partial) {
     const int gx = (tiles * 128 * 32 + 255) / 256;
@@ -1220,363 +907,15 @@ int launch_wgrad(WgradArgs& a, int splits, int flags, hipStream_t st, float* ws 
     if (gy < 1 || a.det) gy = 1;
     SOD_LAUNCH(wgrad_reduce_kernel, dim3(gx, gy), dim3(256), 0, st, a);
   }
-  prof_end(pi, st, 32003, 1.f, 2);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
 
-int fill_wlevel(WgradArgs& a, int l, const void* dy, const void* x, int H, int W, long long dy_img_stride, long long x_img_stride) {
-  if (!dy || !x || H <= 0 || W <= 0) return SOD_EARG;
-  const int Ho = out_size(H, a.pad, a.dil, a.R, a.stride), Wo = out_size(W, a.pad, a.dil, a.S, a.stride);
-  if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-  if (dy_img_stride <= 0) dy_img_stride = (long long)Ho * Wo * a.K;
-  if (x_img_stride <= 0) x_img_stride = (long long)H * W * a.C;
-  const unsigned long long yb = (unsigned long long)a.N * dy_img_stride * 2ull, xb = (unsigned long long)a.N * x_img_stride * 2ull;
-  if (yb >= 0x80000000ull || xb >= 0x80000000ull || (long long)a.N * Ho * Wo >= (1ll << 30)) return SOD_ESIZE;
-  WLevel& g = a.lev[l];
-  g.dy = dy; g.x = x; g.dy_bytes = (uint32_t)yb; g.x_bytes = (uint32_t)xb;
-  g.Hx = H; g.Wx = W; g.Ho = Ho; g.Wo = Wo; g.P = a.N * Ho * Wo;
-  g.dy_img_stride = (int)dy_img_stride; g.x_img_stride = (int)x_img_stride;
-  g.div_hw = make_fastdiv((uint32_t)(Ho * Wo));
-  g.div_w = make_fastdiv((uint32_t)Wo);
+int launch_wgrad_reduce(const WgradArgs& a, hipStream_t st) {
+  const int gx = (a.QT * a.CT * a.R * a.S * 128 * 32 + 255) / 256;
+  SOD_LAUNCH(wgrad_reduce_kernel, dim3(gx, 1), dim3(256), 0, st, a);
+  SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
 
-}  // namespace
-
-static int conv2d_fwd_impl(const void* x, const void* w, const float* bias, const void* res, void* y, void* relu_bits,
-                           int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
-                           long long x_img_stride, long long y_img_stride, long long res_img_stride,
-                           int flags, int out_f32, void* stream) {
-  if (!x || !w || !y) return SOD_EARG;
-  if (relu_bits && (out_f32 || (K & 7) || y_img_stride > 0)) return SOD_EARG;      // bits follow the dense bf16 output
-  const int Ho = out_size(H, pad, dil, R, stride), Wo = out_size(W, pad, dil, S, stride);
-  if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-  ConvArgs a{};
-  const bool cwin = (flags & SOD_CONV_CWIN) != 0;
-  if (cwin && (C != K || (C & 127) || relu_bits)) return SOD_EARG;      // window = the q-tile's own 128 channels; weights [K][R*S][128]
-  int rc = fill_common(a, 1, N, cwin ? 128 : C, K, R, S, stride, pad, dil);
-  if (rc) return rc;
-  if (cwin) { a.Cpitch = C; a.cwin = 1; }
-  rc = fill_level(a, 0, x, y, H, W, Ho, Wo, x_img_stride, y_img_stride, out_f32 ? 4 : 2);
-  if (rc) return rc;
-  a.w = w; a.bias = bias;
-  a.flags = 0;
-  if (bias) a.flags |= F_BIAS;
-  if (flags & SOD_CONV_RELU) a.flags |= F_RELU;
-  if (res) {
-    a.lev[0].res = res;
-    if (flags & SOD_CONV_RES_UP2) {
-      if ((Ho & 1) || (Wo & 1)) return SOD_EARG;
-      a.flags |= F_RES_UP2;
-      a.lev[0].res_img_stride = (int)(res_img_stride > 0 ? res_img_stride : (long long)(Ho / 2) * (Wo / 2) * K);
-    } else {
-      a.flags |= F_RES;
-      a.lev[0].res_img_stride = (int)(res_img_stride > 0 ? res_img_stride : a.lev[0].dst_img_stride);
-    }
-  }
-  if (relu_bits) { a.flags |= F_WBITS; a.lev[0].bits = relu_bits; }
-  if (g_conv_reverse) a.flags |= F_REVERSE;
-  hipStream_t st = (hipStream_t)stream;
-  return out_f32 ? dispatch_conv<MODE_FWD, true>(a, st) : dispatch_conv<MODE_FWD, false>(a, st);
-}
-
-extern "C" int sod_conv2d_fwd(const void* x, const void* w, const float* bias, const void* res, void* y,
-                              int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
-                              long long x_img_stride, long long y_img_stride, long long res_img_stride,
-                              int flags, int out_f32, void* stream) {
-  return conv2d_fwd_impl(x, w, bias, res, y, nullptr, N, H, W, C, K, R, S, stride, pad, dil, x_img_stride, y_img_stride, res_img_stride, flags,
-                         out_f32, stream);
-}
-
-extern "C" int sod_conv2d_fwd_bits(const void* x, const void* w, const float* bias, const void* res, void* y, void* relu_bits,
-                                   int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil, int flags, void* stream) {
-  if (!relu_bits) return SOD_EARG;
-  return conv2d_fwd_impl(x, w, bias, res, y, relu_bits, N, H, W, C, K, R, S, stride, pad, dil, 0, 0, 0, flags, 0, stream);
-}
-
-extern "C" int sod_conv2d_fwd_ml(int nlev, const void* const* x, const void* w, const float* bias, void* const* y,
-                                 int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                 long long y_img_stride, int flags, int out_f32, void* stream) {
-  if (!x || !w || !y || !H || !W) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, C, K, R, S, stride, pad, dil);
-  if (rc) return rc;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, stride), Wo = out_size(W[l], pad, dil, S, stride);
-    if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-    rc = fill_level(a, l, x[l], y[l], H[l], W[l], Ho, Wo, 0, y_img_stride, out_f32 ? 4 : 2);
-    if (rc) return rc;
-  }
-  a.w = w; a.bias = bias;
-  a.flags = (bias ? F_BIAS : 0) | ((flags & SOD_CONV_RELU) ? F_RELU : 0);
-  hipStream_t st = (hipStream_t)stream;
-  return out_f32 ? dispatch_conv<MODE_FWD, true>(a, st) : dispatch_conv<MODE_FWD, false>(a, st);
-}
-
-extern "C" int sod_conv2d_fwd_ml_gnsum(int nlev, const void* const* x, const void* w, const float* bias, void* const* y,
-                                       int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                       long long y_img_stride, int flags, float* gn_sums, int G, void* stream) {
-  if (!x || !w || !y || !H || !W || !gn_sums) return SOD_EARG;
-  if (G <= 0 || K != G * 8) return SOD_EARG;          // a lane's 8 output channels must be exactly one group
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, C, K, R, S, stride, pad, dil);
-  if (rc) return rc;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, stride), Wo = out_size(W[l], pad, dil, S, stride);
-    if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-    rc = fill_level(a, l, x[l], y[l], H[l], W[l], Ho, Wo, 0, y_img_stride, 2);
-    if (rc) return rc;
-    a.lev[l].gn_sum = gn_sums + (size_t)l * N * G * 2;
-  }
-  a.w = w; a.bias = bias;
-  a.gn_G = G;
-  a.flags = (bias ? F_BIAS : 0) | ((flags & SOD_CONV_RELU) ? F_RELU : 0) | F_GNSTATS;
-  hipStream_t st = (hipStream_t)stream;
-  hipError_t e = hipMemsetAsync(gn_sums, 0, sizeof(float) * 2 * (size_t)N * G * nlev, st);
-  if (e != hipSuccess) return (int)e;
-  return dispatch_conv<MODE_FWD, false>(a, st);
-}
-
-extern "C" int sod_conv2d_dgrad(const void* dy, const void* wt, const void* accum, const void* relu_mask, void* dx,
-                                int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                long long dy_img_stride, long long dx_img_stride, void* stream) {
-  if (!dy || !wt || !dx) return SOD_EARG;
-  const int Ho = out_size(H, pad, dil, R, stride), Wo = out_size(W, pad, dil, S, stride);
-  if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-  ConvArgs a{};
-  // GEMM rows are the INPUT pixels (H,W); the gather source is dY (Ho,Wo,K); output channels = C.
-  int rc = fill_common(a, 1, N, K, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  rc = fill_level(a, 0, dy, dx, Ho, Wo, H, W, dy_img_stride, dx_img_stride, 2);
-  if (rc) return rc;
-  a.w = wt; a.bias = nullptr;
-  a.flags = 0;
-  if (accum) { a.flags |= F_RES; a.lev[0].res = accum; a.lev[0].res_img_stride = a.lev[0].dst_img_stride; }
-  if (relu_mask) { a.flags |= F_MASK; a.lev[0].mask = relu_mask; }
-  if (g_conv_reverse) a.flags |= F_REVERSE;
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-// Data gradient of a grouped convolution in window mode (see SOD_CONV_CWIN): wt_win is [C][R*S][128], row c holds, per tap, the weights
-// towards the 128 output channels of c's own 128-channel tile.  C == K, multiples of 128.
-extern "C" int sod_conv2d_dgrad_cwin(const void* dy, const void* wt_win, const void* relu_mask, void* dx,
-                                     int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil, void* stream) {
-  if (!dy || !wt_win || !dx || C != K || (C & 127)) return SOD_EARG;
-  const int Ho = out_size(H, pad, dil, R, stride), Wo = out_size(W, pad, dil, S, stride);
-  if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, 1, N, 128, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  a.Cpitch = K; a.cwin = 1;
-  rc = fill_level(a, 0, dy, dx, Ho, Wo, H, W, 0, 0, 2);
-  if (rc) return rc;
-  a.w = wt_win; a.bias = nullptr;
-  a.flags = 0;
-  if (relu_mask) { a.flags |= F_MASK; a.lev[0].mask = relu_mask; }
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-extern "C" int sod_conv2d_dgrad_bits(const void* dy, const void* wt, const void* accum, int accum_even, const void* relu_bits, void* dx,
-                                     int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil, void* stream) {
-  if (!dy || !wt || !dx || !relu_bits || (C & 7)) return SOD_EARG;
-  if (accum_even && (!accum || (H & 1) || (W & 1))) return SOD_EARG;
-  const int Ho = out_size(H, pad, dil, R, stride), Wo = out_size(W, pad, dil, S, stride);
-  if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, 1, N, K, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  rc = fill_level(a, 0, dy, dx, Ho, Wo, H, W, 0, 0, 2);
-  if (rc) return rc;
-  a.w = wt; a.bias = nullptr;
-  a.flags = F_MASKBITS;
-  a.lev[0].mask = relu_bits;
-  if (accum && accum_even) {       // accum is (N, H/2, W/2, C): the compact data gradient of a stride-2 1x1 consumer
-    a.flags |= F_RES_UP2 | F_RES_EVEN; a.lev[0].res = accum; a.lev[0].res_img_stride = (H / 2) * (W / 2) * C;
-  } else if (accum) {
-    a.flags |= F_RES; a.lev[0].res = accum; a.lev[0].res_img_stride = a.lev[0].dst_img_stride;
-  }
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-extern "C" int sod_conv2d_dgrad_ml(int nlev, const void* const* dy, const void* wt, void* const* dx,
-                                   int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                   long long dy_img_stride, void* stream) {
-  if (!dy || !wt || !dx || !H || !W) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, K, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, stride), Wo = out_size(W[l], pad, dil, S, stride);
-    if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-    rc = fill_level(a, l, dy[l], dx[l], Ho, Wo, H[l], W[l], dy_img_stride, 0, 2);
-    if (rc) return rc;
-  }
-  a.w = wt; a.bias = nullptr; a.flags = 0;
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-extern "C" int sod_conv2d_dgrad_ml_mask(int nlev, const void* const* dy, const void* wt, const void* const* relu_mask, void* const* dx,
-                                        int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                        long long dy_img_stride, void* stream) {
-  if (!dy || !wt || !dx || !relu_mask || !H || !W) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, K, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, stride), Wo = out_size(W[l], pad, dil, S, stride);
-    if (Ho <= 0 || Wo <= 0 || !relu_mask[l]) return SOD_EARG;
-    rc = fill_level(a, l, dy[l], dx[l], Ho, Wo, H[l], W[l], dy_img_stride, 0, 2);
-    if (rc) return rc;
-    a.lev[l].mask = relu_mask[l];
-  }
-  a.w = wt; a.bias = nullptr; a.flags = F_MASK;
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-// sod_conv2d_dgrad_ml for dY rows of `Kpitch` channels contracted as Kp >= Kpitch channels per tap (Kp a multiple of 64): wt_pad is
-// [C][R][S][Kp] with zero columns from Kpitch on; the 16-byte chunks of the K loop that lie past a pixel's last channel are requested out
-// of range (zero fill), never read from the next pixel or from behind the buffer.  A contraction that is no multiple of 64 channels per tap
-// (RetinaNet's 720 class scores) otherwise takes the per-chunk gather path of the 128x128 kernel; padded to 768 it runs on the linear K
-// loops, i.e. on the 256x256 kernel for the tower-sized output.  stride 1 only.
-extern "C" int sod_conv2d_dgrad_ml_kpitch(int nlev, const void* const* dy, const void* wt_pad, void* const* dx,
-                                          int N, const int* H, const int* W, int C, int Kp, int Kpitch, int R, int S, int pad, int dil,
-                                          long long dy_img_stride, void* stream) {
-  if (!dy || !wt_pad || !dx || !H || !W || Kpitch <= 0 || (Kpitch & 7) || Kp < Kpitch || (Kp & 63)) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, Kp, C, R, S, 1, pad, dil);
-  if (rc) return rc;
-  a.Cpitch = Kpitch;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, 1), Wo = out_size(W[l], pad, dil, S, 1);
-    if (Ho <= 0 || Wo <= 0) return SOD_EARG;
-    rc = fill_level(a, l, dy[l], dx[l], Ho, Wo, H[l], W[l], dy_img_stride, 0, 2);
-    if (rc) return rc;
-  }
-  a.w = wt_pad; a.bias = nullptr; a.flags = 0;
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-// sod_conv2d_dgrad_ml whose epilogue adds accum[l] (bf16, dx[l]'s shape) to level l's result: the SECOND of two consumers of the same
-// tensors (the two FCOS towers read the same FPN outputs, fcosv2.py:342-361; the objectness and anchor-delta convs of the RPN head read the
-// same hidden tensor) leaves the sum of both data gradients in one pass; relu_mask (optional, per level): the post-ReLU tensors the sum is
-// the gradient of - the ReLU backward is applied after the addition (dX = mask > 0 ? dX + accum : 0).
-extern "C" int sod_conv2d_dgrad_ml_accum(int nlev, const void* const* dy, const void* wt, const void* const* accum, const void* const* relu_mask,
-                                         void* const* dx, int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                         long long dy_img_stride, void* stream) {
-  if (!dy || !wt || !dx || !accum || !H || !W) return SOD_EARG;
-  ConvArgs a{};
-  int rc = fill_common(a, nlev, N, K, C, R, S, stride, pad, dil);
-  if (rc) return rc;
-  for (int l = 0; l < nlev; ++l) {
-    const int Ho = out_size(H[l], pad, dil, R, stride), Wo = out_size(W[l], pad, dil, S, stride);
-    if (Ho <= 0 || Wo <= 0 || !accum[l]) return SOD_EARG;
-    rc = fill_level(a, l, dy[l], dx[l], Ho, Wo, H[l], W[l], dy_img_stride, 0, 2);
-    if (rc) return rc;
-    a.lev[l].res = accum[l];
-    a.lev[l].res_img_stride = a.lev[l].dst_img_stride;
-    if (relu_mask) {
-      if (!relu_mask[l]) return SOD_EARG;
-      a.lev[l].mask = relu_mask[l];
-    }
-  }
-  a.w = wt; a.bias = nullptr; a.flags = F_RES | (relu_mask ? F_MASK : 0);
-  return dispatch_conv<MODE_DGRAD, false>(a, (hipStream_t)stream);
-}
-
-extern "C" int sod_conv_last_variant(void) { return g_last_variant; }
-
-extern "C" int sod_conv_prof_enable(int on) {
-  ConvProf& p = g_prof;
-  if (on && !p.ev) {
-    constexpr int CAP = 8192;
-    p.ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * CAP);
-    p.variant = (int*)malloc(sizeof(int) * CAP);
-    p.mode = (int*)malloc(sizeof(int) * CAP);
-    p.frac = (float*)malloc(sizeof(float) * CAP);
-    if (!p.ev || !p.variant || !p.mode || !p.frac) return SOD_EARG;
-    for (int i = 0; i < 2 * CAP; ++i)
-      if (hipEventCreate(&p.ev[i]) != hipSuccess) return SOD_EARG;
-    p.cap = CAP;
-  }
-  p.on.store(on ? 1 : 0);
-  return SOD_OK;
-}
-
-extern "C" int sod_conv_prof_collect(float* ms, int* variant, float* frac, int* mode, int max) {
-  ConvProf& p = g_prof;
-  const int have = p.n.load();
-  const int n = have < max ? have : max;
-  if (n > 0 && (!ms || !variant || !frac || !mode)) return SOD_EARG;
-  for (int i = 0; i < n; ++i) {
-    if (hipEventSynchronize(p.ev[2 * i + 1]) != hipSuccess) return SOD_EARG;
-    float t = 0.f;
-    if (hipEventElapsedTime(&t, p.ev[2 * i], p.ev[2 * i + 1]) != hipSuccess) return SOD_EARG;
-    ms[i] = t; variant[i] = p.variant[i]; frac[i] = p.frac[i]; mode[i] = p.mode[i];
-  }
-  p.n.store(0);
-  return n;
-}
-
-// the single-level forward / data-gradient launches that follow walk their tiles last to first (see F_REVERSE)
-extern "C" int sod_conv_set_reverse(int on) {
-  g_conv_reverse = on ? 1 : 0;
-  return SOD_OK;
-}
-
-extern "C" int sod_conv_set_wgrad_variant(int variant) {
-  if (variant < -1) return SOD_EARG;
-  g_wgrad_variant = variant;
-  return SOD_OK;
-}
-
-extern "C" int sod_conv_set_ws3(int mode) {
-  if (mode < -1 || mode > 2) return SOD_EARG;
-  g_conv_ws3 = mode;
-  return SOD_OK;
-}
-
-extern "C" int sod_conv_set_pw(int on) {
-  if (on < -1 || on > 1) return SOD_EARG;
-  g_conv_pw = on;
-  return SOD_OK;
-}
-
-extern "C" int sod_conv_set_tile256(int mode) {
-  if (mode < -1 || mode > 2) return SOD_EARG;
-  g_conv256_mode = mode;
-  return SOD_OK;
-}
-
-extern "C" int sod_conv2d_wgrad(const void* dy, const void* x, float* dw, const float* qscale,
-                                int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                long long dy_img_stride, long long x_img_stride, int splits, int flags,
-                                void* ws, long long ws_bytes, void* stream) {
-  if (!dy || !x || !dw || ws_bytes < 0 || ((uintptr_t)ws & 15)) return SOD_EARG;
-  if (N <= 0 || C <= 0 || K <= 0 || (C & 7) || (K & 7) || R <= 0 || S <= 0 || stride <= 0 || dil <= 0 || pad < 0) return SOD_EARG;
-  WgradArgs a{};
-  a.nlev = 1; a.dw = dw; a.qscale = qscale; a.N = N; a.C = C; a.K = K;
-  a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.dil = dil;
-  int rc = fill_wlevel(a, 0, dy, x, H, W, dy_img_stride, x_img_stride);
-  if (rc) return rc;
-  return launch_wgrad(a, splits, flags, (hipStream_t)stream, (float*)ws, ws ? ws_bytes : 0);
-}
-
-// Workspace that lets every shape of one launch take the slab path: one 256x256 fp32 partial tile per CU plus the rounding of the
-// split count, doubled for grids of more than one round (tiles > CUs).
-extern "C" long long sod_conv2d_wgrad_workspace_bytes(void) { return 160ll << 20; }
-
-extern "C" int sod_conv2d_wgrad_ml(int nlev, const void* const* dy, const void* const* x, float* dw, const float* qscale,
-                                   int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
-                                   long long dy_img_stride, int splits, int flags, void* ws, long long ws_bytes, void* stream) {
-  if (!dy || !x || !dw || !H || !W || nlev <= 0 || nlev > MAXLEV || ws_bytes < 0 || ((uintptr_t)ws & 15)) return SOD_EARG;
-  if (N <= 0 || C <= 0 || K <= 0 || (C & 7) || (K & 7) || R <= 0 || S <= 0 || stride <= 0 || dil <= 0 || pad < 0) return SOD_EARG;
-  WgradArgs a{};
-  a.nlev = nlev; a.dw = dw; a.qscale = qscale; a.N = N; a.C = C; a.K = K;
-  a.R = R; a.S = S; a.stride = stride; a.pad = pad; a.dil = dil;
-  for (int l = 0; l < nlev; ++l) {
-    int rc = fill_wlevel(a, l, dy[l], x[l], H[l], W[l], dy_img_stride, 0);
-    if (rc) return rc;
-  }
-  return launch_wgrad(a, splits, flags, (hipStream_t)stream, (float*)ws, ws ? ws_bytes : 0);
-}
+}  // namespace sodconv

@@ -431,13 +431,9 @@ int launch256(const ConvArgs& a0, int max_pt_tiles, hipStream_t st) {
     tiles += (a.lev[l].P + 255) / 256;
   }
   a.np_tiles = (max_pt_tiles > 0 && max_pt_tiles < tiles) ? max_pt_tiles : tiles;
-  auto kern = conv_igemm256_kernel<MODE, OUT_F32>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  constexpr auto kern = conv_igemm256_kernel<MODE, OUT_F32>;
+  const hipError_t e = sod_max_dynamic_lds_once<kern>(LDS_BYTES);
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(kern, dim3(a.nq_tiles * a.np_tiles), dim3(512), LDS_BYTES, st, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;

@@ -277,13 +277,9 @@ template <int MODE, int CK, int KS, int PT, int NX>
 int launch_pw_one(const ConvArgs& a, hipStream_t st) {
   constexpr int C = CK * 32, QW = 128 * KS;
   constexpr int lds = NX * PT * C * 2 + 2 * PT * QW * 2 + 2 * (PT * QW / 8 < 1024 ? 1024 : PT * QW / 8) + 1024;
-  auto kern = conv_pw_kernel<MODE, CK, KS, PT, NX>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  constexpr auto kern = conv_pw_kernel<MODE, CK, KS, PT, NX>;
+  const hipError_t e = sod_max_dynamic_lds_once<kern>(lds);
+  if (e != hipSuccess) return (int)e;
   const int nq = a.Nout / QW;
   const int grid = 256;                         // one workgroup per CU (pw_supported checks the device)
   const int stride = grid / nq;                 // pixel-tile streams

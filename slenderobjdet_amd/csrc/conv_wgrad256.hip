@@ -373,12 +373,8 @@ int launch_wgrad256(WgradArgs& a, int cus, float* ws, long long ws_bytes, hipStr
   if (!ws || need > ws_bytes) return SOD_EARG;
   if ((long long)tiles * 16384 >= (1ll << 31)) return SOD_ESIZE;
   a.partial = ws;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad256_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, WLDS_BYTES);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  const hipError_t e = sod_max_dynamic_lds_once<conv_wgrad256_kernel>(WLDS_BYTES);
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(conv_wgrad256_kernel, dim3(a.nz * tiles), dim3(512), WLDS_BYTES, st, a);
   SOD_LAUNCH(wgrad256_reduce_kernel, dim3(tiles * 64), dim3(256), 0, st, a);
   SOD_CHECK_LAUNCH();

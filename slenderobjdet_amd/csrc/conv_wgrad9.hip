@@ -420,12 +420,8 @@ int launch_wgrad9(const WgradArgs& a, int cus, float* ws, long long ws_bytes, hi
   if (!ws || need > ws_bytes) return SOD_EARG;
   if ((long long)tiles * 18432 >= (1ll << 31)) return SOD_ESIZE;
   w.partial = ws;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)conv_wgrad9_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G9_LDS + 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  const hipError_t e = sod_max_dynamic_lds_once<conv_wgrad9_kernel>(G9_LDS + 1024);
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(conv_wgrad9_kernel, dim3(w.nz * tiles), dim3(512), G9_LDS + 1024, st, w);
   SOD_LAUNCH(wgrad9_reduce_kernel, dim3(tiles * 72), dim3(256), 0, st, w);
   SOD_CHECK_LAUNCH();

@@ -5,7 +5,7 @@
 //   kernel of conv_wgrad256.hip does not take)
 //
 // The backbone shapes have few output tiles (4 ... 72 of 128 x 128) for 256 CUs, so the contraction over pixels is split and the
-// partial tiles have to meet somewhere.  conv_wgrad_kernel (conv_igemm.hip) runs two 4-wave workgroups per CU and lets all 512 of them
+// partial tiles have to meet somewhere.  conv_wgrad_kernel (conv_igemm.hip, launch_wgrad128) runs two 4-wave workgroups per CU and lets all 512 of them
 // add their 64-KB tile into dW with float atomics: 32 MB of atomics per launch at the memory side's 1.3 TB/s, issued by every block at
 // the same moment at the end of the launch, as 64-B segments (one 16x16 accumulator register = 4 rows x 64 B).  Here a workgroup is G
 // groups of 4 waves; every group runs the SAME ring loop as that kernel (three or four 16-KB LDS slots per group, filled by
@@ -14,7 +14,7 @@
 //     tile, then all 4 G waves walk the rows - half the partial bytes per CU leave the CU for G = 2;
 //   * that pass also changes the layout: a wave instruction of the global epilogue covers 256 CONTIGUOUS bytes of one dW row (the shape
 //     MI355X_MICROARCH.md measures at the full atomic rate), or, with a workspace (EPI = 1), the combined tile goes out as a [128][128]
-//     slab with 16-B stores and wgrad_reduce_kernel (conv_igemm.hip) sums the slabs of a tile in fixed order: no atomics;
+//     slab with 16-B stores and wgrad_reduce_kernel (conv_igemm.hip, launch_wgrad_reduce) sums the slabs of a tile in fixed order: no atomics;
 //   (Round 4 also built fragment double-buffering - the 16 transposing reads of K-step it+1 issued before the MFMAs of step it - and a
 //   four-slot ring; both measured neutral, profiles/r4_wgrad_variants.txt, and left the tree in round 5.)
 // One barrier per K-step for the whole workgroup; groups whose pixel range is shorter (the last split) keep staging dead (zero-fill)
@@ -339,13 +339,9 @@ template <int G, int NSTAGE, int EPI, int ABL = 0>
 int launch_one(const WgradArgs& a, int tiles, hipStream_t st) {
   constexpr int ring = G * NSTAGE * RSTAGE, comb = G * 64 * TPITCH * 4;
   constexpr int lds = ring > comb ? ring : comb;
-  auto kern = conv_wgrad_ring_kernel<G, NSTAGE, EPI, ABL>;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  constexpr auto kern = conv_wgrad_ring_kernel<G, NSTAGE, EPI, ABL>;
+  const hipError_t e = sod_max_dynamic_lds_once<kern>(lds);
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(kern, dim3(a.nz * tiles), dim3(256 * G), lds, st, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;

@@ -236,13 +236,9 @@ bool ws3_supported(const ConvArgs& a, int mode, bool out_f32, int cus, bool any_
 int launch_ws3(const ConvArgs& a, int mode, hipStream_t st) {
   const LevelGeo& g = a.lev[0];
   const int ty = (g.Hs + W3_TH - 1) / W3_TH, tx = (g.Ws + W3_TW - 1) / W3_TW;
-  static bool attr_done[2] = {false, false};
-  const void* kern = mode == MODE_FWD ? (const void*)conv_ws3_kernel<MODE_FWD> : (const void*)conv_ws3_kernel<MODE_DGRAD>;
-  if (!attr_done[mode]) {
-    hipError_t e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, W3_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_done[mode] = true;
-  }
+  const hipError_t e = mode == MODE_FWD ? sod_max_dynamic_lds_once<conv_ws3_kernel<MODE_FWD>>(W3_LDS)
+                                        : sod_max_dynamic_lds_once<conv_ws3_kernel<MODE_DGRAD>>(W3_LDS);
+  if (e != hipSuccess) return (int)e;
   if (mode == MODE_FWD) SOD_LAUNCH(conv_ws3_kernel<MODE_FWD>, dim3(256), dim3(256), W3_LDS, st, a, ty, tx);
   else SOD_LAUNCH(conv_ws3_kernel<MODE_DGRAD>, dim3(256), dim3(256), W3_LDS, st, a, ty, tx);
   SOD_CHECK_LAUNCH();

@@ -575,12 +575,8 @@ extern "C" int sod_deform_conv_fwd_fused(const void* x, const float* offset, con
   const int rc = dcn_fill(a, x, offset, mask, N, H, W, C, K, KH, KW, stride, pad, dil, deformable_groups, off_ld, mask_ld, mask_is_logit);
   if (rc) return rc;
   a.w = (const __bf16*)w; a.bias = bias; a.y = (__bf16*)y; a.relu = relu;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)dcn_fwd_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, F_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  const hipError_t e = sod_max_dynamic_lds_once<dcn_fwd_fused_kernel>(F_LDS);
+  if (e != hipSuccess) return (int)e;
   const int nq = (K + 255) / 256, np = (a.P + 127) / 128;
   SOD_LAUNCH(dcn_fwd_fused_kernel, dim3(nq * np), dim3(512), F_LDS, (hipStream_t)stream, a);
   SOD_CHECK_LAUNCH();
@@ -600,21 +596,15 @@ extern "C" int sod_deform_conv_wgrad_fused(const void* dy, const void* x, const 
   a.QT = (K + 255) / 256; a.CT = (C + 127) / 128;
   const int tiles = a.QT * a.CT * KH * KW;
   const int KT = (a.P + 63) / 64;
-  int cus = 0, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0) cus = 256;
-  int nz = cus / tiles;
+  int nz = device_cus() / tiles;
   if (nz < 1) nz = 1;
   if (nz > KT) nz = KT;
   const int per = (KT + nz - 1) / nz;
   nz = (KT + per - 1) / per;
   a.nz = nz; a.kt_per_split = per;
   if ((long long)nz * tiles * G_SLAB * (long long)sizeof(float) > ws_bytes) return SOD_EARG;
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)dcn_wgrad_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, G_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  const hipError_t e = sod_max_dynamic_lds_once<dcn_wgrad_fused_kernel>(G_LDS);
+  if (e != hipSuccess) return (int)e;
   hipStream_t st = (hipStream_t)stream;
   SOD_LAUNCH(dcn_wgrad_fused_kernel, dim3(nz * tiles), dim3(512), G_LDS, st, a);
   SOD_LAUNCH(dcn_wgrad_reduce_kernel, dim3(tiles * 32), dim3(256), 0, st, a);

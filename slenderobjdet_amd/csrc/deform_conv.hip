@@ -817,20 +817,13 @@ extern "C" int sod_deform_conv_bwd_fused(const void* dy, const void* wt, const v
   SOD_LAUNCH(dcn_wnorm_kernel, dim3((rows + 255) / 256), dim3(256), 0, st, (const __bf16*)wt, rows, K, wnorm_ws);
   const int tiles_x = (a.Wo + 7) / 8, tiles_y = (a.Ho + 7) / 8;
   const dim3 grid(tiles_x * tiles_y, C / 32, N);
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipSuccess;
-    const void* kernels[12] = {
-        (const void*)dcn_bwd_fused_kernel<4, false, false>, (const void*)dcn_bwd_fused_kernel<8, false, false>, (const void*)dcn_bwd_fused_kernel<16, false, false>,
-        (const void*)dcn_bwd_fused_kernel<4, true, false>,  (const void*)dcn_bwd_fused_kernel<8, true, false>,  (const void*)dcn_bwd_fused_kernel<16, true, false>,
-        (const void*)dcn_bwd_fused_kernel<4, false, true>,  (const void*)dcn_bwd_fused_kernel<8, false, true>,  (const void*)dcn_bwd_fused_kernel<16, false, true>,
-        (const void*)dcn_bwd_fused_kernel<4, true, true>,   (const void*)dcn_bwd_fused_kernel<8, true, true>,   (const void*)dcn_bwd_fused_kernel<16, true, true>};
-    for (int i = 0; i < 12 && e == hipSuccess; ++i) e = hipFuncSetAttribute(kernels[i], hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
-#define SOD_DCN_BWD_LAUNCH(KS_, GM_, STG_) \
-  SOD_LAUNCH((dcn_bwd_fused_kernel<KS_, GM_, STG_>), grid, dim3(256), lds, st, a, (const __bf16*)dy, (const __bf16*)wt, wnorm_ws, tiles_x, WH, WW, r_env)
+#define SOD_DCN_BWD_LAUNCH(KS_, GM_, STG_)                                                                                           \
+  do {                                                                                                                               \
+    const hipError_t e_ = sod_max_dynamic_lds_once<dcn_bwd_fused_kernel<KS_, GM_, STG_>>(96 * 1024);                                 \
+    if (e_ != hipSuccess) return (int)e_;                                                                                            \
+    SOD_LAUNCH((dcn_bwd_fused_kernel<KS_, GM_, STG_>), grid, dim3(256), lds, st, a, (const __bf16*)dy, (const __bf16*)wt, wnorm_ws, tiles_x, WH, WW, \
+               r_env);                                                                                                               \
+  } while (0)
 #define SOD_DCN_BWD_PICK(GM_, STG_) \
   do { if (K == 128) SOD_DCN_BWD_LAUNCH(4, GM_, STG_); else if (K == 256) SOD_DCN_BWD_LAUNCH(8, GM_, STG_); else SOD_DCN_BWD_LAUNCH(16, GM_, STG_); } while (0)
   if (a.dmask) { if (staged) SOD_DCN_BWD_PICK(true, true); else SOD_DCN_BWD_PICK(true, false); }

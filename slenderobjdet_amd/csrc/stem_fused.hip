@@ -180,12 +180,8 @@ extern "C" int sod_stem_fused(int n, const void* const* imgs, const int* H, cons
   a.Hc = (Hp + 6 - 7) / 2 + 1; a.Wc = (Wp + 6 - 7) / 2 + 1;
   a.Hq = (a.Hc + 2 - 3) / 2 + 1; a.Wq = (a.Wc + 2 - 3) / 2 + 1;
   for (int c = 0; c < 3; ++c) { a.mean[c] = mean3[c]; a.stdv[c] = std3[c]; }
-  static bool attr_done = false;
-  if (!attr_done) {
-    hipError_t e = hipFuncSetAttribute((const void*)stem_fused_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, ST_LDS);
-    if (e != hipSuccess) return (int)e;
-    attr_done = true;
-  }
+  const hipError_t e = sod_max_dynamic_lds_once<stem_fused_kernel>(ST_LDS);
+  if (e != hipSuccess) return (int)e;
   SOD_LAUNCH(stem_fused_kernel, dim3((a.Wq + 7) / 8, (a.Hq + 7) / 8, n), dim3(256), ST_LDS, (hipStream_t)stream, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
