@@ -747,6 +747,25 @@ int sod_proposal_ar(const int* gt_off, const float* gt_box, const int* gt_cls, c
                     int T, const float* ratio_rng, int R, const float* area_rng, int A, const long long* scratch_off, float* scratch,
                     int* hits, int* counts, float* recalls, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * COCO box evaluation for rotated boxes (train_net.py:60-62 builds detectron2's RotatedCOCOEvaluator for datasets of evaluator type
+ * "rotated_coco": RotatedCOCOeval.computeIoU over pycocotools' COCOeval.evaluateImg; host side in
+ * slenderobjdet_amd/evaluation/rotated_coco_evaluation.py).  Segments, offsets, outputs and the host parameter limits as sod_coco_match;
+ * the result feeds sod_coco_accumulate unchanged.
+ *
+ * sod_coco_match_rotated: gt_box5 [G, 5] / dt_box5 [N, 5] float32 (cx, cy, w, h, angle in degrees).  The IoU is detectron2's
+ *   pairwise_iou_rotated(dt, gt) in float32 (the function behind sod_box_iou_rotated, detection first) and has no crowd form; the scan
+ *   compares in float32, starting from float32(min(iou_thr[t], 1 - 1e-10)); a crowd gt is ignored and can be matched again.  The range
+ *   test is generic: gt g is ignored for range a when gt_crowd[g] or gt_val[g] < lo[a] or gt_val[g] > hi[a], an unmatched detection
+ *   when dt_val[d] is outside [lo[a], hi[a]] (gt_val [G], dt_val [N] float64: areas for COCO's area ranges, side ratios for the
+ *   slenderness ranges).  scratch_off [num_seg]: offset in floats (even) of the segment's slot in `scratch` (8-byte aligned), needed
+ *   where sod_coco_match_rotated_scratch_floats(G, max_det) > 0. */
+long long sod_coco_match_rotated_scratch_floats(int num_gts, int max_det);
+int sod_coco_match_rotated(const int* gt_off, const float* gt_box5, const unsigned char* gt_crowd, const double* gt_val,
+                           const int* dt_off, const float* dt_box5, const double* dt_val, int num_seg, int num_img, int max_det,
+                           const double* iou_thr, int T, const double* ranges, int A, const long long* scratch_off, float* scratch,
+                           unsigned long long* dt_matched, unsigned long long* dt_ignored, int* npig, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

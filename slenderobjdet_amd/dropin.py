@@ -7,6 +7,12 @@
 The training hot path and the slender-object COCO box evaluation (slenderobjdet_amd.evaluation) are backed by real code;
 TTA, the rotated evaluator and dataset names resolve to objects that raise ``NotImplementedError`` when used (out of scope,
 SURVEY.md §2.1).
+
+The rotated evaluator exists (slenderobjdet_amd.evaluation.RotatedCOCOEvaluator) but is bound on request only, so that importing
+this module keeps what it has always bound:
+
+    import slenderobjdet_amd.dropin as dropin
+    dropin.bind_rotated_evaluator()      # detectron2.evaluation.RotatedCOCOEvaluator is now the real class
 """
 import sys
 import types
@@ -102,6 +108,12 @@ def install():
     _mod("slender_det.layers", Scale=_nn.Scale, iou_loss=_losses.iou_loss, DFConv2d=_dcn.DFConv2d)
     _mod("slender_det.checkpoint", DetectionCheckpointer=_engine.defaults._Checkpointer)
     _mod("slender_det.evaluation", COCOEvaluator=_evaluation.COCOEvaluator, inference_on_dataset=_evaluation.inference_on_dataset)
+
+
+def bind_rotated_evaluator():
+    """Rebinds ``detectron2.evaluation.RotatedCOCOEvaluator`` (a stub after ``install()``) to the on-device evaluator; returns it."""
+    _mod("detectron2.evaluation", RotatedCOCOEvaluator=_evaluation.RotatedCOCOEvaluator)
+    return _evaluation.RotatedCOCOEvaluator
 
 
 install()

@@ -101,6 +101,23 @@ class CocoGt:
         self.anns = list(self.dataset.get("annotations", []))
         self.ratios = np.array([float(gt_ratio(a)) for a in self.anns], np.float64)
         self._arrays = None
+        self._rotated_arrays = None
+
+    def _segment_order(self):
+        """(image index of every annotation or -1, the annotations of known images and categories ordered by (category, image)
+        segment and json order within, seg_gt_off [K*I+1])."""
+        I, K = len(self.img_ids), len(self.cat_ids)
+        img_idx = {im: i for i, im in enumerate(self.img_ids)}
+        cat_idx = {c: k for k, c in enumerate(self.cat_ids)}
+        img_of = np.array([img_idx.get(a["image_id"], -1) for a in self.anns], np.int64)
+        cat_of = np.array([cat_idx.get(a["category_id"], -1) for a in self.anns], np.int64)
+        keep = (img_of >= 0) & (cat_of >= 0)
+        seg = cat_of * I + img_of
+        order = np.nonzero(keep)[0]
+        order = order[np.argsort(seg[order], kind="stable")]
+        seg_gt_off = np.zeros(K * I + 1, np.int32)
+        np.cumsum(np.bincount(seg[order], minlength=K * I), out=seg_gt_off[1:])
+        return img_of, order, seg_gt_off
 
     def arrays(self):
         """Flat numpy arrays of the kernels' gt side (cached):
@@ -108,20 +125,11 @@ class CocoGt:
         img_gt_off [I+1] / img_box [G',4] f32 / img_cls [G'] i32 / img_ratio [G'] f32 - non-crowd gts by image for the recall pass."""
         if self._arrays is not None:
             return self._arrays
-        I, K = len(self.img_ids), len(self.cat_ids)
-        img_idx = {im: i for i, im in enumerate(self.img_ids)}
-        cat_idx = {c: k for k, c in enumerate(self.cat_ids)}
+        I = len(self.img_ids)
         n = len(self.anns)
-        img_of = np.array([img_idx.get(a["image_id"], -1) for a in self.anns], np.int64)
-        cat_of = np.array([cat_idx.get(a["category_id"], -1) for a in self.anns], np.int64)
+        img_of, order, seg_gt_off = self._segment_order()
         box = np.array([a["bbox"][:4] for a in self.anns], np.float64).reshape(n, 4)
         crowd = np.array([1 if a.get("iscrowd", 0) else 0 for a in self.anns], np.uint8)
-        keep = (img_of >= 0) & (cat_of >= 0)
-        seg = cat_of * I + img_of
-        order = np.nonzero(keep)[0]
-        order = order[np.argsort(seg[order], kind="stable")]
-        seg_gt_off = np.zeros(K * I + 1, np.int32)
-        np.cumsum(np.bincount(seg[order], minlength=K * I), out=seg_gt_off[1:])
         # recall pass: the non-crowd gts of each image, class mapped through the metadata map
         ar_keep = np.nonzero((img_of >= 0) & (np.array([a["iscrowd"] == 0 for a in self.anns], bool) if n else np.zeros(0, bool)))[0]
         ar_keep = ar_keep[np.argsort(img_of[ar_keep], kind="stable")]
@@ -134,3 +142,35 @@ class CocoGt:
             img_ratio=self.ratios[ar_keep].astype(np.float32),
         )
         return self._arrays
+
+    def rotated_arrays(self):
+        """The gt side of the rotated-box evaluation (detectron2's RotatedCOCOeval), in the segment order of arrays() (cached):
+        seg_gt_off [K*I+1] / seg_box5 [G,5] f32 (cx, cy, w, h, angle_deg) / seg_crowd [G] u8 / seg_area [G] f64 / seg_ratio5 [G] f64.
+        A five-number ``bbox`` is taken as it is; an XYWH one becomes (x + w/2, y + h/2, w, h, 0) in float32.  seg_area is the
+        annotation's ``area``, else w * h; seg_ratio5 an explicit ``ratio``, else min(w, h) / max(w, h) of the box.  Raises
+        ValueError for a dataset that holds both a five-number box and a crowd gt: the rotated IoU has no crowd form."""
+        if self._rotated_arrays is not None:
+            return self._rotated_arrays
+        n = len(self.anns)
+        _, order, seg_gt_off = self._segment_order()
+        five = [len(a["bbox"]) == 5 for a in self.anns]
+        if any(len(a["bbox"]) not in (4, 5) for a in self.anns):
+            raise ValueError("a bbox must hold 4 (XYWH) or 5 (cx, cy, w, h, angle) numbers")
+        if any(five) and any(a.get("iscrowd", 0) for a in self.anns):
+            raise ValueError("a dataset with rotated (five-number) boxes must not hold crowd annotations")
+        box5 = np.zeros((n, 5), np.float32)
+        area = np.zeros(n, np.float64)
+        ratio = np.zeros(n, np.float64)
+        for j, a in enumerate(self.anns):
+            b = np.array(a["bbox"], np.float32)
+            if five[j]:
+                box5[j] = b
+            else:
+                box5[j] = (b[0] + b[2] / np.float32(2), b[1] + b[3] / np.float32(2), b[2], b[3], 0)
+            w, h = float(a["bbox"][2]), float(a["bbox"][3])
+            area[j] = float(a["area"]) if "area" in a else w * h
+            ratio[j] = float(a["ratio"]) if "ratio" in a else (min(w, h) / max(w, h) if max(w, h) > 0 else 0.0)
+        crowd = np.array([1 if (a.get("iscrowd", 0) or a.get("ignore", 0)) else 0 for a in self.anns], np.uint8)
+        self._rotated_arrays = dict(seg_gt_off=seg_gt_off, seg_box5=np.ascontiguousarray(box5[order]), seg_crowd=crowd[order],
+                                    seg_area=area[order], seg_ratio5=ratio[order])
+        return self._rotated_arrays

@@ -6,7 +6,11 @@ match kernel) / accumulate (ordering + the accumulate kernel) / ar (ordering + t
 after a warm-up; the kernel launches of one evaluation (torch profiler); the wall time of the whole evaluate including the host
 summaries; and a hash of the output arrays.
 
-    python tools/bench_coco_eval.py [--images 5000] [--cats 80] [--dets 100] [--iters 5] [--seed 0]
+    python tools/bench_coco_eval.py [--images 5000] [--cats 80] [--dets 100] [--iters 5] [--seed 0] [--rotated]
+
+``--rotated`` times RotatedCOCOEvaluator.evaluate_flat on ``synthetic_rotated_coco`` at the same size (match / accumulate phases;
+there is no recall pass) and reports the share of the (detection, gt) pairs of the segments whose circumscribed circles meet, i.e.
+that go on towards the polygon clipping.
 """
 import argparse
 import hashlib
@@ -22,9 +26,9 @@ import numpy as np  # noqa: E402
 import torch  # noqa: E402
 
 from slenderobjdet_amd.data.catalog import MetadataCatalog  # noqa: E402
-from slenderobjdet_amd.evaluation import COCOEvaluator  # noqa: E402
+from slenderobjdet_amd.evaluation import COCOEvaluator, RotatedCOCOEvaluator  # noqa: E402
 from slenderobjdet_amd.evaluation.coco_evaluation import predictions_from_numpy  # noqa: E402
-from slenderobjdet_amd.evaluation.synthetic import synthetic_coco  # noqa: E402
+from slenderobjdet_amd.evaluation.synthetic import synthetic_coco, synthetic_rotated_coco  # noqa: E402
 
 
 def _launches(ev, flat):
@@ -42,6 +46,30 @@ def _launches(ev, flat):
         return None, None
 
 
+def _circle_share(ds, preds):
+    """(pairs of the (image, category) segments, those whose circumscribed circles meet) - iou_rotated_impl's first early return."""
+    cats = sorted(c["id"] for c in ds["categories"])
+    gts = {}
+    for a in ds["annotations"]:
+        gts.setdefault(a["image_id"], []).append([cats.index(a["category_id"])] + list(a["bbox"][:4]))
+    order = np.argsort(preds["image_id"], kind="stable")
+    img_s = preds["image_id"][order]
+    starts = np.flatnonzero(np.r_[True, img_s[1:] != img_s[:-1], True])
+    pairs = near = 0
+    for b, e in zip(starts[:-1], starts[1:]):
+        g = np.array(gts.get(int(img_s[b]), []), np.float64).reshape(-1, 5)
+        if not len(g):
+            continue
+        sel = order[b:e]
+        d, c = preds["boxes"][sel].astype(np.float64), preds["category"][sel]
+        same = c[:, None] == g[None, :, 0]
+        rs = 0.5 * np.hypot(d[:, 2], d[:, 3])[:, None] + 0.5 * np.hypot(g[:, 3], g[:, 4])[None]
+        d2 = (d[:, 0, None] - g[None, :, 1]) ** 2 + (d[:, 1, None] - g[None, :, 2]) ** 2
+        pairs += int(same.sum())
+        near += int((same & (d2 <= rs * rs * 1.0001)).sum())
+    return pairs, near
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--images", type=int, default=5000)
@@ -50,10 +78,12 @@ def main():
     ap.add_argument("--iters", type=int, default=5)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--rotated", action="store_true", help="time the rotated-box evaluation (RotatedCOCOEvaluator)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()
-    ds, preds = synthetic_coco(a.seed, n_images=a.images, n_cats=a.cats, dets_per_image=(a.dets, a.dets), no_dt=0.0)
+    synth = synthetic_rotated_coco if a.rotated else synthetic_coco
+    ds, preds = synth(a.seed, n_images=a.images, n_cats=a.cats, dets_per_image=(a.dets, a.dets), no_dt=0.0)
     t_gen = time.perf_counter() - t0
     with tempfile.TemporaryDirectory() as tmp:
         jf = os.path.join(tmp, "gt.json")
@@ -61,7 +91,7 @@ def main():
             json.dump(ds, f)
         MetadataCatalog.get("bench_coco_eval").json_file = jf
         t0 = time.perf_counter()
-        ev = COCOEvaluator("bench_coco_eval", None, False)
+        ev = (RotatedCOCOEvaluator if a.rotated else COCOEvaluator)("bench_coco_eval", None, False)
         t_gt = time.perf_counter() - t0
     flat = predictions_from_numpy(preds, dev)
     ev.evaluate_flat(flat)          # warm-up: gt upload, scratch layout, code objects
@@ -77,22 +107,27 @@ def main():
         wall.append(time.perf_counter() - w0)
         e = {k: v[0] for k, v in events.items()}
         split["match"].append(e["match"].elapsed_time(e["accumulate"]))
-        split["accumulate"].append(e["accumulate"].elapsed_time(e["ar"]))
-        split["ar"].append(e["ar"].elapsed_time(e["end"]))
+        split["accumulate"].append(e["accumulate"].elapsed_time(e["end" if a.rotated else "ar"]))
+        if not a.rotated:
+            split["ar"].append(e["ar"].elapsed_time(e["end"]))
         split["total"].append(e["match"].elapsed_time(e["end"]))
     h = hashlib.sha256()
-    for arr in (ev.precision, ev.recall, ev.scores, ev.recalls.numpy()):
+    for arr in (ev.precision, ev.recall, ev.scores) + (() if a.rotated else (ev.recalls.numpy(),)):
         h.update(np.ascontiguousarray(arr).tobytes())
     n_all, n_ours = (None, None) if a.no_profile else _launches(ev, flat)
     out = {
         "metric": "coco_eval_device_ms", "images": a.images, "categories": a.cats, "detections": int(len(preds["score"])),
         "gts": len(ds["annotations"]),
-        "device_ms": {k: round(float(np.median(v)), 3) for k, v in split.items()},
+        "device_ms": {k: round(float(np.median(v)), 3) for k, v in split.items() if v},
         "evaluate_wall_ms": round(float(np.median(wall)) * 1e3, 3),
         "gt_index_s": round(t_gt, 3), "synth_s": round(t_gen, 3),
         "kernel_launches": n_all, "coco_kernel_launches": n_ours,
-        "AP": res["bbox"]["AP"], "AR@100": res["ar"]["AR@100"], "output_sha256": h.hexdigest()[:16],
+        "AP": res["bbox"]["AP"], **({} if a.rotated else {"AR@100": res["ar"]["AR@100"]}), "output_sha256": h.hexdigest()[:16],
     }
+    if a.rotated:
+        pairs, near = _circle_share(ds, preds)
+        out.update(metric="rotated_coco_eval_device_ms", AR100=float(ev.stats[8] * 100), segment_pairs=pairs,
+                   pairs_past_circle_test=near, share_past_circle_test=round(near / max(pairs, 1), 4))
     print(json.dumps(out))
 
 
