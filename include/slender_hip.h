@@ -349,6 +349,37 @@ int sod_fcos_regctr_loss_bwd(const float* box_raw, int ld_box, const float* ctr_
                              const float* grad_reg, const float* grad_ctr, const float* norm, float inv_world,
                              void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr, int dctr_col,
                              float* dscales, float* ws, void* stream);
+/* FCOSTopK targets (slender_det/modeling/meta_arch/fcos/fcos_topk.py:24-101): sod_fcos_assign plus, for every gt box g, the
+ * `topk` (1..8; the reference hard-codes 5, :39) foreground locations assigned to g with the largest centerness target
+ * (:79-90; all of them when there are no more than `topk`).  labels / reg_targets / ctr_targets are bit-identical to
+ * sod_fcos_assign on the same input.  gt_index [N,L]: index into the concatenated gt list of the box a foreground location was
+ * given to (locations_to_gt_inds, :71), -1 on background.  sel [N,L] uint8: the selection (topk_locations, :78-91).  Ties at the
+ * cut, which torch.topk(sorted=False) leaves open (:86): higher centerness first, then lower location index.  An image without
+ * gt is all background with nothing selected (the reference raises there).
+ * stats3 = {number of positives, sum of centerness targets over the SELECTED locations, the same over ALL foreground locations};
+ * stats3[0..2) is what sod_fcos_finalize_losses and `norm` of sod_fcos_regctr_loss_sel_bwd take (:197-215).  Block / wave partials
+ * are added in a fixed order: reproducible from run to run.  No host synchronisation. */
+int sod_fcos_assign_topk(const float* boxes, const int* classes, const int* box_offsets, int N,
+                         int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
+                         const float* lvl_lo, const float* lvl_hi, float radius, int num_classes, int topk,
+                         int* labels, float* reg_targets, float* ctr_targets, int* gt_index, unsigned char* sel,
+                         float* stats3, float* ws, void* stream);
+/* FCOSTopK.losses, regression + centerness part (fcos_topk.py:208-229): sod_fcos_regctr_loss_fwd / _bwd / _bwd_f32 whose IoU
+ * term, box gradient and d(scales) run only on rows with sel != 0 (:222-225); the centerness BCE term and its gradient stay on
+ * all foreground rows (:227-229).  norm[1] is the sum of centerness targets over the selected rows (:211-215). */
+int sod_fcos_regctr_loss_sel_fwd(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
+                                 const int* labels, const float* reg_targets, const float* ctr_targets,
+                                 const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
+                                 const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
+                                 const unsigned char* sel, float* sums, float* ws, void* stream);
+int sod_fcos_regctr_loss_sel_bwd(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
+                                 const int* labels, const float* reg_targets, const float* ctr_targets,
+                                 const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
+                                 const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
+                                 const unsigned char* sel,
+                                 const float* grad_reg, const float* grad_ctr, const float* norm, float inv_world,
+                                 void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr, int dctr_col,
+                                 float* dscales, float* ws, void* stream);
 /* out3 = {cls_loss, reg_loss, centerness_loss} with the all-reduced normalisers (fcosv2.py:115-145) */
 int sod_fcos_finalize_losses(const float* focal_sum, const float* regctr_sums, const float* stats,
                              float inv_world, float* out3, void* stream);
@@ -708,6 +739,13 @@ int sod_fcos_regctr_loss_bwd_f32(const float* box_raw, int ld_box, const float* 
                                  const int* lvl_w, const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
                                  const float* grad_reg, const float* grad_ctr, const float* norm, float inv_world, void* dbox, int ld_out,
                                  int ctr_col, void* dctr, int ld_dctr, int dctr_col, float* dscales, float* ws, void* stream);
+/* sod_fcos_regctr_loss_sel_bwd with fp32 gradient rows */
+int sod_fcos_regctr_loss_sel_bwd_f32(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr, const int* labels,
+                                     const float* reg_targets, const float* ctr_targets, const float* scales, int N, int nlevels,
+                                     const int* lvl_h, const int* lvl_w, const int* lvl_stride, int num_classes, int loss_type,
+                                     int norm_reg_targets, const unsigned char* sel, const float* grad_reg, const float* grad_ctr,
+                                     const float* norm, float inv_world, void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr,
+                                     int dctr_col, float* dscales, float* ws, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Slender-object COCO box evaluation (slender_det/evaluation/cocoeval.py, coco_evaluation.py; host side in

@@ -77,6 +77,10 @@ _SIGS = {
     "sod_fcos_regctr_loss_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P],
     "sod_fcos_regctr_loss_bwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _F,
                                  _P, _I, _I, _P, _I, _I, _P, _P, _P],
+    "sod_fcos_assign_topk": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sod_fcos_regctr_loss_sel_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "sod_fcos_regctr_loss_sel_bwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _F,
+                                     _P, _I, _I, _P, _I, _I, _P, _P, _P],
     "sod_fcos_finalize_losses": [_P, _P, _P, _F, _P, _P],
     "sod_nms_workspace_bytes": [_I],
     "sod_fcos_decode": [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
@@ -152,6 +156,8 @@ _SIGS = {
     "sod_weight_prep_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
     "sod_fcos_regctr_loss_bwd_f32": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _F,
                                      _P, _I, _I, _P, _I, _I, _P, _P, _P],
+    "sod_fcos_regctr_loss_sel_bwd_f32": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _F,
+                                         _P, _I, _I, _P, _I, _I, _P, _P, _P],
     "sod_sample_labels": [_P, _I, _I, _I, _F, _I, ctypes.c_ulonglong, _P, _P, _P],
     "sod_sample_labels_list": [_P, _I, _I, _I, _F, _I, ctypes.c_ulonglong, _P, _P, _P, _P, _P],
     "sod_compact_samples": [_P, _I, _I, _I, _P, _P, _P],

@@ -305,12 +305,16 @@ struct AssignArgs {
   float lvl_lo[SOD_MAX_LEVELS], lvl_hi[SOD_MAX_LEVELS], lvl_rad[SOD_MAX_LEVELS];  // rad = stride*radius (fp32), <=0: box test
   int nlevels;
   int* labels; float* reg; float* ctr;
+  int* gt_index; unsigned char* sel;       // fcos_assign_kernel<true> only: [N,L] index of the owning gt (-1: background), selection cleared
+  int lvl_h[SOD_MAX_LEVELS];               // fcos_topk_select_kernel only
+  int topk;
 };
 
 __device__ __forceinline__ float centerness_of(float l, float t, float r, float b) {
   return sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(t, b) / fmaxf(t, b)));
 }
 
+template <bool WITH_INDEX>
 __global__ __launch_bounds__(256) void fcos_assign_kernel(const AssignArgs a, float* __restrict__ part) {
   __shared__ float red[4];
   const int n = blockIdx.y;
@@ -357,21 +361,116 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(const AssignArgs a, fl
     }
     int label = a.num_classes;
     float c = 0.f;
+    int owner = -1;
     if (g1 > g0 && best != 100000000.f) {
       label = a.classes[bi];
-      if (label >= 0 && label != a.num_classes) { c = centerness_of(bl, bt, br, bb); npos += 1.f; sctr += c; }
+      if (label >= 0 && label != a.num_classes) { c = centerness_of(bl, bt, br, bb); npos += 1.f; sctr += c; owner = bi; }
     }
     const long long o = (long long)n * a.L + loc;
     a.labels[o] = label;
     *reinterpret_cast<f32x4_t*>(a.reg + o * 4) = f32x4_t{bl, bt, br, bb};
     a.ctr[o] = c;
+    if constexpr (WITH_INDEX) { a.gt_index[o] = owner; a.sel[o] = 0; }
   }
   npos = block_sum_256(npos, red);
   sctr = block_sum_256(sctr, red);
   if (threadIdx.x == 0) {
     const int b = blockIdx.y * gridDim.x + blockIdx.x;
     part[b] = npos;
-    part[RED_BLOCKS + b] = sctr;
+    part[(WITH_INDEX ? 2 : 1) * RED_BLOCKS + b] = sctr;      // <true>: slot 1 belongs to the selection pass (stats3 order)
+  }
+}
+
+// ---------------------------------------------------------------------------------------------
+// Top-k positive locations of every gt box (reference: fcos_topk.py:78-91, a host loop over images x gts with nonzero / .item() /
+// topk).  One wave per gt box; the wave walks only the location rectangle the box (or its centre-sampling region) covers on every
+// level whose size-of-interest range the box can meet, and keeps the locations whose gt_index (written by fcos_assign_kernel<true>) is
+// this box.  The k winners of the order (centerness descending, then location index ascending) come out of k rounds of a wave-wide
+// arg-max over a 64-bit key, each round restricted to keys below the previous winner: no per-lane list, nothing dynamically indexed.
+// A box with at most k positives therefore selects all of them.  The second of two identical boxes owns no location (the first
+// minimum wins in the assignment) and selects nothing.
+// ---------------------------------------------------------------------------------------------
+constexpr int TOPK_BLOCKS = 128;            // 4 waves each: 512 waves stride over the gt boxes, one partial sum per wave
+constexpr int TOPK_MAX = 8;
+
+__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned int hi = __shfl_xor((unsigned int)(v >> 32), o, 64), lo = __shfl_xor((unsigned int)v, o, 64);
+    const unsigned long long w = ((unsigned long long)hi << 32) | lo;
+    v = (w > v) ? w : v;
+  }
+  return v;
+}
+
+// first / last grid index of a level (size n, stride st) whose location i*st + st/2 can lie in [lo, hi]: one cell of slack on either
+// side (membership is decided by gt_index, this only bounds the walk), clamped in floating point so that any box stays in range
+__device__ __forceinline__ void cell_range(float lo, float hi, int st, int n, int& i0, int& i1) {
+  const float half = (float)(st / 2), inv = 1.f / (float)st, top = (float)(n - 1);
+  i0 = (int)fminf(fmaxf(floorf((lo - half) * inv) - 1.f, 0.f), top);
+  i1 = (int)fminf(fmaxf(ceilf((hi - half) * inv) + 1.f, 0.f), top);
+}
+
+__global__ __launch_bounds__(256) void fcos_topk_select_kernel(const AssignArgs a, float* __restrict__ part /* [TOPK_BLOCKS*4] */) {
+  const int lane = threadIdx.x & 63;
+  const int wave = blockIdx.x * 4 + (threadIdx.x >> 6), nwaves = gridDim.x * 4;
+  const int G = a.box_off[a.N];
+  float ssel = 0.f;
+  for (int g = wave; g < G; g += nwaves) {
+    int n = 0;
+    while (n + 1 < a.N && g >= a.box_off[n + 1]) ++n;
+    const float x1 = a.boxes[g * 4 + 0], y1 = a.boxes[g * 4 + 1], x2 = a.boxes[g * 4 + 2], y2 = a.boxes[g * 4 + 3];
+    const float side = fmaxf(x2 - x1, y2 - y1);
+    const int* __restrict__ own = a.gt_index + (long long)n * a.L;
+    const float* __restrict__ ctr = a.ctr + (long long)n * a.L;
+    unsigned long long bound = ~0ull;       // keys of this round must be below the previous winner's
+    for (int k = 0; k < a.topk; ++k) {
+      unsigned long long best = 0ull;       // 0 = no candidate: a real key has a non-zero low word (location < 2^31)
+      for (int lv = 0; lv < a.nlevels; ++lv) {
+        // a location inside the box sees max(l,t,r,b) in [side/2, side): levels whose range cannot meet that hold no positive of it
+        if (side * 0.5f > a.lvl_hi[lv] + 1.f || side < a.lvl_lo[lv] - 1.f) continue;
+        const int st = a.lvl_stride[lv];
+        float xa = x1, ya = y1, xb = x2, yb = y2;
+        if (a.lvl_rad[lv] > 0.f) {
+          const float cx = (x1 + x2) / 2.f, cy = (y1 + y2) / 2.f, rad = a.lvl_rad[lv];
+          xa = fmaxf(xa, cx - rad); ya = fmaxf(ya, cy - rad); xb = fminf(xb, cx + rad); yb = fminf(yb, cy + rad);
+        }
+        int ix0, ix1, iy0, iy1;
+        cell_range(xa, xb, st, a.lvl_w[lv], ix0, ix1);
+        cell_range(ya, yb, st, a.lvl_h[lv], iy0, iy1);
+        if (ix1 < ix0 || iy1 < iy0) continue;
+        const int rw = ix1 - ix0 + 1, cells = rw * (iy1 - iy0 + 1);
+        for (int c = lane; c < cells; c += 64) {
+          const int ry = c / rw, rx = c - ry * rw;
+          const int loc = a.lvl_off[lv] + (iy0 + ry) * a.lvl_w[lv] + ix0 + rx;
+          if (own[loc] != g) continue;
+          const unsigned long long key = ((unsigned long long)__float_as_uint(ctr[loc]) << 32) | (unsigned int)(0x7fffffff - loc);
+          if (key < bound && key > best) best = key;
+        }
+      }
+      best = wave_max_u64(best);
+      if (best == 0ull) break;              // wave-uniform: fewer than k positives
+      bound = best;
+      if (lane == 0) {
+        const int loc = 0x7fffffff - (int)(unsigned int)(best & 0xffffffffull);
+        a.sel[(long long)n * a.L + loc] = 1;
+        ssel += __uint_as_float((unsigned int)(best >> 32));
+      }
+    }
+  }
+  if (lane == 0) part[RED_BLOCKS + wave] = ssel;
+}
+
+// stats3 = {sum part[0..n0), sum part[RED_BLOCKS..+n1), sum part[2 RED_BLOCKS..+n2)}: fixed order, as finish_sum_kernel
+__global__ void finish_sum3_kernel(const float* __restrict__ part, int n0, int n1, int n2, float* __restrict__ out) {
+  __shared__ float red[4];
+  for (int s = 0; s < 3; ++s) {
+    const int nblk = s == 0 ? n0 : (s == 1 ? n1 : n2);
+    float v = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) v += part[s * RED_BLOCKS + i];
+    v = block_sum_256(v, red);
+    if (threadIdx.x == 0) out[s] = v;
+    __syncthreads();
   }
 }
 
@@ -387,6 +486,7 @@ struct RegCtrArgs {
   const float* scales;                    // [nlevels] device
   int M, L, num_classes, type, norm_reg;
   int nlevels; int lvl_off[SOD_MAX_LEVELS + 1]; int lvl_stride[SOD_MAX_LEVELS];
+  const unsigned char* sel;               // <SEL = true> only: [M], the IoU term runs on rows with sel != 0 (fcos_topk.py:222-225)
 };
 
 __device__ __forceinline__ int level_of(const RegCtrArgs& a, int loc) {
@@ -395,6 +495,7 @@ __device__ __forceinline__ int level_of(const RegCtrArgs& a, int loc) {
   return lv;
 }
 
+template <bool SEL>
 __global__ __launch_bounds__(256) void regctr_fwd_kernel(const RegCtrArgs a, float* __restrict__ part) {
   __shared__ float red[4];
   float lreg = 0.f, lctr = 0.f;
@@ -411,7 +512,7 @@ __global__ __launch_bounds__(256) void regctr_fwd_kernel(const RegCtrArgs a, flo
       t[e] = a.reg_t[(long long)i * 4 + e];
     }
     const float c = a.ctr_t[i];
-    lreg += iou_ltrb<false>(p, t, a.type).loss * c;
+    if (!SEL || a.sel[i]) lreg += iou_ltrb<false>(p, t, a.type).loss * c;
     const float x = a.ctr_logit[(long long)i * a.ld_ctr];
     lctr += fmaxf(x, 0.f) - x * c + log1pf(expf(-fabsf(x)));
   }
@@ -422,7 +523,7 @@ __global__ __launch_bounds__(256) void regctr_fwd_kernel(const RegCtrArgs a, flo
 
 // writes d(box_raw) and d(ctr_logit) as bf16 into a padded [M, ld_out] buffer (columns 0..3 box, ctr_col ctr,
 // remaining columns zero) and per-level d(scale) partials.
-template <typename T>      // T = __bf16 (product path) or float (fp32-storage validation path, f32_path.hip)
+template <typename T, bool SEL>      // T = __bf16 (product path) or float (fp32-storage validation path, f32_path.hip)
 __global__ __launch_bounds__(256) void regctr_bwd_kernel(const RegCtrArgs a, const float* __restrict__ greg,
                                                          const float* __restrict__ gctr, const float* __restrict__ norm, float inv_world,
                                                          T* __restrict__ dbox, int ld_out, int ctr_col,
@@ -452,17 +553,19 @@ __global__ __launch_bounds__(256) void regctr_bwd_kernel(const RegCtrArgs a, con
         t[e] = a.reg_t[(long long)i * 4 + e];
       }
       const float c = a.ctr_t[i];
-      const IouOut o = iou_ltrb<true>(p, t, a.type);
-      float ds = 0.f;
+      if (!SEL || a.sel[i]) {               // rows outside the selection: no box gradient, no d(scale) (the centerness term stays)
+        const IouOut o = iou_ltrb<true>(p, t, a.type);
+        float ds = 0.f;
 #pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float dp = o.g[e] * c * sreg;
-        const float dz = a.norm_reg ? ((z[e] > 0.f) ? dp * (float)a.lvl_stride[lv] : 0.f) : dp * p[e];
-        gb[e] = dz * s;
-        ds += dz * raw[e];
+        for (int e = 0; e < 4; ++e) {
+          const float dp = o.g[e] * c * sreg;
+          const float dz = a.norm_reg ? ((z[e] > 0.f) ? dp * (float)a.lvl_stride[lv] : 0.f) : dp * p[e];
+          gb[e] = dz * s;
+          ds += dz * raw[e];
+        }
+#pragma unroll
+        for (int l = 0; l < SOD_MAX_LEVELS; ++l) if (l == lv) dsc[l] += ds;
       }
-#pragma unroll
-      for (int l = 0; l < SOD_MAX_LEVELS; ++l) if (l == lv) dsc[l] += ds;
       const float x = a.ctr_logit[(long long)i * a.ld_ctr];
       gc = (1.f / (1.f + expf(-x)) - c) * sctr;
     }
@@ -587,30 +690,61 @@ extern "C" int sod_iou_loss_bwd(const float* pred, const float* target, const fl
   return SOD_OK;
 }
 
-extern "C" int sod_fcos_assign(const float* boxes, const int* classes, const int* box_offsets, int N,
-                               int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
-                               const float* lvl_lo, const float* lvl_hi, float radius, int num_classes,
-                               int* labels, float* reg_targets, float* ctr_targets, float* stats /*[2]*/, float* ws, void* stream) {
-  if (!box_offsets || !labels || !reg_targets || !ctr_targets || !stats || !ws || N <= 0 || nlevels <= 0 || nlevels > SOD_MAX_LEVELS)
-    return SOD_EARG;
-  AssignArgs a{};
+static int fill_assign(AssignArgs& a, const float* boxes, const int* classes, const int* box_offsets, int N,
+                       int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
+                       const float* lvl_lo, const float* lvl_hi, float radius, int num_classes,
+                       int* labels, float* reg_targets, float* ctr_targets, int& gx) {
+  if (!box_offsets || !labels || !reg_targets || !ctr_targets || N <= 0 || nlevels <= 0 || nlevels > SOD_MAX_LEVELS) return SOD_EARG;
   a.boxes = boxes; a.classes = classes; a.box_off = box_offsets; a.N = N; a.num_classes = num_classes; a.nlevels = nlevels;
   int off = 0;
   for (int l = 0; l < nlevels; ++l) {
     if (lvl_h[l] <= 0 || lvl_w[l] <= 0 || lvl_stride[l] <= 0) return SOD_EARG;
-    a.lvl_off[l] = off; a.lvl_w[l] = lvl_w[l]; a.lvl_stride[l] = lvl_stride[l];
+    a.lvl_off[l] = off; a.lvl_w[l] = lvl_w[l]; a.lvl_h[l] = lvl_h[l]; a.lvl_stride[l] = lvl_stride[l];
     a.lvl_lo[l] = lvl_lo[l]; a.lvl_hi[l] = lvl_hi[l];
     a.lvl_rad[l] = radius > 0.f ? (float)((double)lvl_stride[l] * (double)radius) : 0.f;
     off += lvl_h[l] * lvl_w[l];
   }
   for (int l = nlevels; l <= SOD_MAX_LEVELS; ++l) a.lvl_off[l] = off;
   a.L = off; a.labels = labels; a.reg = reg_targets; a.ctr = ctr_targets;
-  int gx = (a.L + 255) / 256;
+  gx = (a.L + 255) / 256;
   if (gx * N > RED_BLOCKS) gx = RED_BLOCKS / N;
   if (gx < 1) return SOD_EARG;
+  return SOD_OK;
+}
+
+extern "C" int sod_fcos_assign(const float* boxes, const int* classes, const int* box_offsets, int N,
+                               int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
+                               const float* lvl_lo, const float* lvl_hi, float radius, int num_classes,
+                               int* labels, float* reg_targets, float* ctr_targets, float* stats /*[2]*/, float* ws, void* stream) {
+  if (!stats || !ws) return SOD_EARG;
+  AssignArgs a{};
+  int gx = 0;
+  const int rc = fill_assign(a, boxes, classes, box_offsets, N, nlevels, lvl_h, lvl_w, lvl_stride, lvl_lo, lvl_hi, radius, num_classes,
+                             labels, reg_targets, ctr_targets, gx);
+  if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
-  SOD_LAUNCH(fcos_assign_kernel, dim3(gx, N), dim3(256), 0, st, a, ws);
+  SOD_LAUNCH(fcos_assign_kernel<false>, dim3(gx, N), dim3(256), 0, st, a, ws);
   SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, gx * N, 2, stats, 0);
+  SOD_CHECK_LAUNCH();
+  return SOD_OK;
+}
+
+extern "C" int sod_fcos_assign_topk(const float* boxes, const int* classes, const int* box_offsets, int N,
+                                    int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
+                                    const float* lvl_lo, const float* lvl_hi, float radius, int num_classes, int topk,
+                                    int* labels, float* reg_targets, float* ctr_targets, int* gt_index, unsigned char* sel,
+                                    float* stats3, float* ws, void* stream) {
+  if (!stats3 || !ws || !gt_index || !sel || topk < 1 || topk > TOPK_MAX) return SOD_EARG;
+  AssignArgs a{};
+  int gx = 0;
+  const int rc = fill_assign(a, boxes, classes, box_offsets, N, nlevels, lvl_h, lvl_w, lvl_stride, lvl_lo, lvl_hi, radius, num_classes,
+                             labels, reg_targets, ctr_targets, gx);
+  if (rc) return rc;
+  a.gt_index = gt_index; a.sel = sel; a.topk = topk;
+  hipStream_t st = (hipStream_t)stream;
+  SOD_LAUNCH(fcos_assign_kernel<true>, dim3(gx, N), dim3(256), 0, st, a, ws);              // partials: slot 0 num_pos, slot 2 sum ctr
+  SOD_LAUNCH(fcos_topk_select_kernel, dim3(TOPK_BLOCKS), dim3(256), 0, st, a, ws);         // slot 1: sum ctr over the selection
+  SOD_LAUNCH(finish_sum3_kernel, dim3(1), dim3(256), 0, st, ws, gx * N, TOPK_BLOCKS * 4, gx * N, stats3);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -624,34 +758,47 @@ static int fill_regctr(RegCtrArgs& a, int nlevels, const int* lvl_h, const int* 
   return SOD_OK;
 }
 
-extern "C" int sod_fcos_regctr_loss_fwd(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
-                                        const int* labels, const float* reg_targets, const float* ctr_targets,
-                                        const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
-                                        const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
-                                        float* sums /*[2]: reg, ctr*/, float* ws, void* stream) {
-  if (!box_raw || !ctr_logit || !labels || !reg_targets || !ctr_targets || !scales || !sums || !ws) return SOD_EARG;
+#define SOD_REGCTR_PARAMS                                                                                                        \
+  const float *box_raw, int ld_box, const float *ctr_logit, int ld_ctr, const int *labels, const float *reg_targets,                   \
+      const float *ctr_targets, const float *scales, int N, int nlevels, const int *lvl_h, const int *lvl_w, const int *lvl_stride,    \
+      int num_classes, int loss_type, int norm_reg_targets
+#define SOD_REGCTR_ARGS                                                                                                          \
+  box_raw, ld_box, ctr_logit, ld_ctr, labels, reg_targets, ctr_targets, scales, N, nlevels, lvl_h, lvl_w, lvl_stride, num_classes, \
+      loss_type, norm_reg_targets
+#define SOD_REGCTR_BWD_PARAMS                                                                                              \
+  const float *grad_reg, const float *grad_ctr, const float *norm /*[2]*/, float inv_world, void *dbox, int ld_out, int ctr_col, \
+      void *dctr, int ld_dctr, int dctr_col, float *dscales, float *ws, void *stream
+#define SOD_REGCTR_BWD_ARGS grad_reg, grad_ctr, norm, inv_world, dbox, ld_out, ctr_col, dctr, ld_dctr, dctr_col, dscales, ws, stream
+
+// use_sel = 0: the FCOSV2 entry points (sel ignored); 1: the FCOSTopK ones (sel required)
+static int regctr_fwd_impl(int use_sel, const unsigned char* sel, SOD_REGCTR_PARAMS, float* sums /*[2]: reg, ctr*/, float* ws, void* stream) {
+  if (!box_raw || !ctr_logit || !labels || !reg_targets || !ctr_targets || !scales || !sums || !ws || (use_sel && !sel)) return SOD_EARG;
   RegCtrArgs a{};
   int rc = fill_regctr(a, nlevels, lvl_h, lvl_w, lvl_stride);
   if (rc) return rc;
   a.box_raw = box_raw; a.ld_box = ld_box; a.ctr_logit = ctr_logit; a.ld_ctr = ld_ctr; a.labels = labels;
   a.reg_t = reg_targets; a.ctr_t = ctr_targets; a.scales = scales; a.M = N * a.L; a.num_classes = num_classes;
-  a.type = loss_type; a.norm_reg = norm_reg_targets;
+  a.type = loss_type; a.norm_reg = norm_reg_targets; a.sel = sel;
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(a.M);
-  SOD_LAUNCH(regctr_fwd_kernel, dim3(g), dim3(256), 0, st, a, ws);
+  if (use_sel)
+    SOD_LAUNCH(regctr_fwd_kernel<true>, dim3(g), dim3(256), 0, st, a, ws);
+  else
+    SOD_LAUNCH(regctr_fwd_kernel<false>, dim3(g), dim3(256), 0, st, a, ws);
   SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, 2, sums, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
 
-static int regctr_bwd_impl(int out_f32, const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
-                                        const int* labels, const float* reg_targets, const float* ctr_targets,
-                                        const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
-                                        const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
-                                        const float* grad_reg, const float* grad_ctr, const float* norm /*[2]*/, float inv_world,
-                                        void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr, int dctr_col,
-                                        float* dscales, float* ws, void* stream) {
-  if (!box_raw || !ctr_logit || !labels || !reg_targets || !ctr_targets || !scales || !grad_reg || !grad_ctr || !norm || !dbox || !dctr || !dscales || !ws)
+template <typename T, bool SEL>
+static void launch_regctr_bwd(const RegCtrArgs& a, int g, hipStream_t st, SOD_REGCTR_BWD_PARAMS) {
+  SOD_LAUNCH((regctr_bwd_kernel<T, SEL>), dim3(g), dim3(256), 0, st, a, grad_reg, grad_ctr, norm, inv_world, (T*)dbox, ld_out, ctr_col,
+             (T*)dctr, ld_dctr, dctr_col, ws);
+}
+
+static int regctr_bwd_impl(int out_f32, int use_sel, const unsigned char* sel, SOD_REGCTR_PARAMS, SOD_REGCTR_BWD_PARAMS) {
+  if (!box_raw || !ctr_logit || !labels || !reg_targets || !ctr_targets || !scales || !grad_reg || !grad_ctr || !norm || !dbox || !dctr || !dscales || !ws ||
+      (use_sel && !sel))
     return SOD_EARG;
   if (ld_out < 4 || (dctr == dbox && (ctr_col < 4 || ctr_col >= ld_out))) return SOD_EARG;
   RegCtrArgs a{};
@@ -659,40 +806,43 @@ static int regctr_bwd_impl(int out_f32, const float* box_raw, int ld_box, const 
   if (rc) return rc;
   a.box_raw = box_raw; a.ld_box = ld_box; a.ctr_logit = ctr_logit; a.ld_ctr = ld_ctr; a.labels = labels;
   a.reg_t = reg_targets; a.ctr_t = ctr_targets; a.scales = scales; a.M = N * a.L; a.num_classes = num_classes;
-  a.type = loss_type; a.norm_reg = norm_reg_targets;
+  a.type = loss_type; a.norm_reg = norm_reg_targets; a.sel = sel;
   hipStream_t st = (hipStream_t)stream;
   const int g = grid_for(a.M);
-  if (out_f32)
-    SOD_LAUNCH(regctr_bwd_kernel<float>, dim3(g), dim3(256), 0, st, a, grad_reg, grad_ctr, norm, inv_world, (float*)dbox, ld_out, ctr_col,
-               (float*)dctr, ld_dctr, dctr_col, ws);
-  else
-    SOD_LAUNCH(regctr_bwd_kernel<__bf16>, dim3(g), dim3(256), 0, st, a, grad_reg, grad_ctr, norm, inv_world, (__bf16*)dbox, ld_out, ctr_col,
-               (__bf16*)dctr, ld_dctr, dctr_col, ws);
+  if (out_f32) {
+    if (use_sel) launch_regctr_bwd<float, true>(a, g, st, SOD_REGCTR_BWD_ARGS);
+    else launch_regctr_bwd<float, false>(a, g, st, SOD_REGCTR_BWD_ARGS);
+  } else {
+    if (use_sel) launch_regctr_bwd<__bf16, true>(a, g, st, SOD_REGCTR_BWD_ARGS);
+    else launch_regctr_bwd<__bf16, false>(a, g, st, SOD_REGCTR_BWD_ARGS);
+  }
   SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, nlevels, dscales, 1);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
 
-extern "C" int sod_fcos_regctr_loss_bwd(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
-                                        const int* labels, const float* reg_targets, const float* ctr_targets,
-                                        const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
-                                        const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
-                                        const float* grad_reg, const float* grad_ctr, const float* norm /*[2]*/, float inv_world,
-                                        void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr, int dctr_col,
-                                        float* dscales, float* ws, void* stream) {
-  return regctr_bwd_impl(0, box_raw, ld_box, ctr_logit, ld_ctr, labels, reg_targets, ctr_targets, scales, N, nlevels, lvl_h, lvl_w, lvl_stride, num_classes,
-                         loss_type, norm_reg_targets, grad_reg, grad_ctr, norm, inv_world, dbox, ld_out, ctr_col, dctr, ld_dctr, dctr_col, dscales, ws, stream);
+extern "C" int sod_fcos_regctr_loss_fwd(SOD_REGCTR_PARAMS, float* sums, float* ws, void* stream) {
+  return regctr_fwd_impl(0, nullptr, SOD_REGCTR_ARGS, sums, ws, stream);
 }
 
-extern "C" int sod_fcos_regctr_loss_bwd_f32(const float* box_raw, int ld_box, const float* ctr_logit, int ld_ctr,
-                                        const int* labels, const float* reg_targets, const float* ctr_targets,
-                                        const float* scales, int N, int nlevels, const int* lvl_h, const int* lvl_w,
-                                        const int* lvl_stride, int num_classes, int loss_type, int norm_reg_targets,
-                                        const float* grad_reg, const float* grad_ctr, const float* norm /*[2]*/, float inv_world,
-                                        void* dbox, int ld_out, int ctr_col, void* dctr, int ld_dctr, int dctr_col,
-                                        float* dscales, float* ws, void* stream) {
-  return regctr_bwd_impl(1, box_raw, ld_box, ctr_logit, ld_ctr, labels, reg_targets, ctr_targets, scales, N, nlevels, lvl_h, lvl_w, lvl_stride, num_classes,
-                         loss_type, norm_reg_targets, grad_reg, grad_ctr, norm, inv_world, dbox, ld_out, ctr_col, dctr, ld_dctr, dctr_col, dscales, ws, stream);
+extern "C" int sod_fcos_regctr_loss_sel_fwd(SOD_REGCTR_PARAMS, const unsigned char* sel, float* sums, float* ws, void* stream) {
+  return regctr_fwd_impl(1, sel, SOD_REGCTR_ARGS, sums, ws, stream);
+}
+
+extern "C" int sod_fcos_regctr_loss_bwd(SOD_REGCTR_PARAMS, SOD_REGCTR_BWD_PARAMS) {
+  return regctr_bwd_impl(0, 0, nullptr, SOD_REGCTR_ARGS, SOD_REGCTR_BWD_ARGS);
+}
+
+extern "C" int sod_fcos_regctr_loss_bwd_f32(SOD_REGCTR_PARAMS, SOD_REGCTR_BWD_PARAMS) {
+  return regctr_bwd_impl(1, 0, nullptr, SOD_REGCTR_ARGS, SOD_REGCTR_BWD_ARGS);
+}
+
+extern "C" int sod_fcos_regctr_loss_sel_bwd(SOD_REGCTR_PARAMS, const unsigned char* sel, SOD_REGCTR_BWD_PARAMS) {
+  return regctr_bwd_impl(0, 1, sel, SOD_REGCTR_ARGS, SOD_REGCTR_BWD_ARGS);
+}
+
+extern "C" int sod_fcos_regctr_loss_sel_bwd_f32(SOD_REGCTR_PARAMS, const unsigned char* sel, SOD_REGCTR_BWD_PARAMS) {
+  return regctr_bwd_impl(1, 1, sel, SOD_REGCTR_ARGS, SOD_REGCTR_BWD_ARGS);
 }
 
 extern "C" int sod_fcos_finalize_losses(const float* focal_sum, const float* regctr_sums, const float* stats,

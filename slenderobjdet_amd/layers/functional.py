@@ -948,29 +948,65 @@ def fcos_assign(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_intere
     return labels, reg, ctr, stats
 
 
+def fcos_assign_topk(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_interest, radius, num_classes, topk):
+    """``fcos_assign`` plus the ``topk`` most central positive locations of every gt box (fcos_topk.py:24-101), no host sync.
+    Returns labels, reg_targets, ctr_targets as ``fcos_assign`` (bit-identical), gt_index (N,L) i32 (index into the concatenated gt
+    list on foreground locations, -1 elsewhere), sel (N,L) u8 and stats3 (3,) = [num_pos, sum_ctr over sel, sum_ctr over foreground]."""
+    dev = box_offsets.device
+    _chk(boxes, torch.float32, "boxes"); _chk(classes, torch.int32, "classes"); _chk(box_offsets, torch.int32, "box_offsets")
+    L = sum(h * w for h, w in lvl_hw)
+    labels = torch.empty((N, L), dtype=torch.int32, device=dev)
+    reg = torch.empty((N, L, 4), dtype=torch.float32, device=dev)
+    ctr = torch.empty((N, L), dtype=torch.float32, device=dev)
+    gt_index = torch.empty((N, L), dtype=torch.int32, device=dev)
+    sel = torch.empty((N, L), dtype=torch.uint8, device=dev)
+    stats3 = torch.empty(3, dtype=torch.float32, device=dev)
+    nl = len(lvl_hw)
+    call("sod_fcos_assign_topk", ptr(boxes), ptr(classes), ptr(box_offsets), N, nl,
+         ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
+         ctypes.cast(_int_arr(strides), ctypes.c_void_p),
+         ctypes.cast(_float_arr([s[0] for s in sizes_of_interest]), ctypes.c_void_p),
+         ctypes.cast(_float_arr([s[1] for s in sizes_of_interest]), ctypes.c_void_p),
+         float(radius), num_classes, int(topk), ptr(labels), ptr(reg), ptr(ctr), ptr(gt_index), ptr(sel), ptr(stats3),
+         ptr(reduce_ws(dev)), stream_ptr())
+    return labels, reg, ctr, gt_index, sel, stats3
+
+
 def fcos_regctr_loss_fwd(box_raw, ld_box, ctr_logit, ld_ctr, labels, reg_t, ctr_t, scales, N, lvl_hw, strides, num_classes,
-                         loss_type, norm_reg):
+                         loss_type, norm_reg, sel=None):
+    """``sel`` (N,L) u8: the IoU term only on the selected rows (FCOSTopK); None: every foreground row (FCOSV2)."""
     dev = labels.device
     sums = torch.empty(2, dtype=torch.float32, device=dev)
     nl = len(lvl_hw)
-    call("sod_fcos_regctr_loss_fwd", ptr(box_raw), ld_box, ptr(ctr_logit), ld_ctr, ptr(labels), ptr(reg_t), ptr(ctr_t), ptr(scales), N, nl,
-         ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
-         ctypes.cast(_int_arr(strides), ctypes.c_void_p), num_classes, IOU_TYPES[loss_type], 1 if norm_reg else 0,
-         ptr(sums), ptr(reduce_ws(dev)), stream_ptr())
+    _chk(sel, torch.uint8, "sel")
+    head = (ptr(box_raw), ld_box, ptr(ctr_logit), ld_ctr, ptr(labels), ptr(reg_t), ptr(ctr_t), ptr(scales), N, nl,
+            ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
+            ctypes.cast(_int_arr(strides), ctypes.c_void_p), num_classes, IOU_TYPES[loss_type], 1 if norm_reg else 0)
+    if sel is None:
+        call("sod_fcos_regctr_loss_fwd", *head, ptr(sums), ptr(reduce_ws(dev)), stream_ptr())
+    else:
+        call("sod_fcos_regctr_loss_sel_fwd", *head, ptr(sel), ptr(sums), ptr(reduce_ws(dev)), stream_ptr())
     return sums
 
 
 def fcos_regctr_loss_bwd(box_raw, ld_box, ctr_logit, ld_ctr, labels, reg_t, ctr_t, scales, N, lvl_hw, strides, num_classes,
                          loss_type, norm_reg, grad_reg, grad_ctr, stats, inv_world, dbox, ld_out, ctr_col, dctr, ld_dctr, dctr_col,
-                         dscales):
+                         dscales, sel=None):
+    """``sel`` as in ``fcos_regctr_loss_fwd``; ``stats[1]`` is then the sum of centerness targets over the selected rows."""
     dev = labels.device
     nl = len(lvl_hw)
+    _chk(sel, torch.uint8, "sel")
     # gradient rows in the storage precision: bf16 for the MFMA kernels, fp32 in the validation mode
-    call("sod_fcos_regctr_loss_bwd_f32" if is_f32() else "sod_fcos_regctr_loss_bwd", ptr(box_raw), ld_box, ptr(ctr_logit), ld_ctr, ptr(labels), ptr(reg_t), ptr(ctr_t), ptr(scales), N, nl,
-         ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
-         ctypes.cast(_int_arr(strides), ctypes.c_void_p), num_classes, IOU_TYPES[loss_type], 1 if norm_reg else 0,
-         ptr(grad_reg), ptr(grad_ctr), ptr(stats), float(inv_world), ptr(dbox), ld_out, ctr_col, ptr(dctr), ld_dctr, dctr_col,
-         ptr(dscales), ptr(reduce_ws(dev)), stream_ptr())
+    name = ("sod_fcos_regctr_loss_bwd" if sel is None else "sod_fcos_regctr_loss_sel_bwd") + ("_f32" if is_f32() else "")
+    head = (ptr(box_raw), ld_box, ptr(ctr_logit), ld_ctr, ptr(labels), ptr(reg_t), ptr(ctr_t), ptr(scales), N, nl,
+            ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
+            ctypes.cast(_int_arr(strides), ctypes.c_void_p), num_classes, IOU_TYPES[loss_type], 1 if norm_reg else 0)
+    tail = (ptr(grad_reg), ptr(grad_ctr), ptr(stats), float(inv_world), ptr(dbox), ld_out, ctr_col, ptr(dctr), ld_dctr, dctr_col,
+            ptr(dscales), ptr(reduce_ws(dev)), stream_ptr())
+    if sel is None:
+        call(name, *head, *tail)
+    else:
+        call(name, *head, ptr(sel), *tail)
 
 
 def fcos_finalize_losses(focal_sum, regctr_sums, stats, inv_world):

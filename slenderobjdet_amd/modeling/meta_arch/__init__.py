@@ -1,5 +1,5 @@
 from .build import META_ARCH_REGISTRY, build_model
-from .fcos import FCOS, FCOSV2, FCOSHead
+from .fcos import FCOS, FCOSV2, FCOSHead, FCOSTopK
 from .retinanet import RetinaNet, RetinaNetHead
 from .reppoints import RepPointsDetector
 from .rcnn import GeneralizedRCNN, ProposalNetwork, ProposalVisibleRCNN

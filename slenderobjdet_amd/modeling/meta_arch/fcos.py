@@ -1,4 +1,4 @@
-"""FCOS / FCOSV2 meta-architectures on the HIP kernels.
+"""FCOS / FCOSV2 / FCOSTopK meta-architectures on the HIP kernels.
 
 Mirror of slender_det/modeling/meta_arch/fcos/fcosv2.py:22-381 (``FCOSV2``, what configs/fcos/fcos_R_50_FPN_1x.yaml:3
 selects) and fcos.py:174-582 (``FCOS``): same constructor contract (``cls(cfg)``), same ``forward(batched_inputs)``
@@ -11,7 +11,9 @@ MI355X-first differences in HOW (not WHAT):
     (``nonzero`` at fcosv2.py:112) — the loss kernels run over all locations with the label as mask;
   * the two scalar all-reduces (num_pos, sum of centerness targets; fcosv2.py:116,132) depend only on the targets,
     so they are issued as ONE 2-element all-reduce before the backbone runs and stay on the device: no ``.item()``;
-  * ``Scale`` and ``exp`` of FCOSHead.forward (fcosv2.py:372-378) are fused into the regression-loss kernel.
+  * ``Scale`` and ``exp`` of FCOSHead.forward (fcosv2.py:372-378) are fused into the regression-loss kernel;
+  * ``FCOSTopK`` (fcos_topk.py:102-468, ``META_ARCHITECTURE: "FCOSTopK"``): the k most central positives of every gt box, a host loop
+    over images x gts there (:79-90), come out of the assignment launch as a (N, L) mask (``sod_fcos_assign_topk``).
 """
 import math
 import os
@@ -190,10 +192,12 @@ class FCOSHead(nn.Module):
 
 
 class _FcosHeadLossFn(torch.autograd.Function):
-    """Prediction convs + FCOSV2.losses (fcosv2.py:104-148) as one autograd node over the ten tower outputs."""
+    """Prediction convs + FCOSV2.losses (fcosv2.py:104-148) as one autograd node over the ten tower outputs.  ``sel`` (N, L) uint8 or
+    None: FCOSTopK.losses (fcos_topk.py:184-235) - the IoU term and the box gradient on the selected rows only, ``stats[1]`` their
+    centerness sum; None issues exactly the FCOSV2 launches."""
 
     @staticmethod
-    def forward(ctx, model, scales, labels, reg_t, ctr_t, stats, inv_world, *towers):
+    def forward(ctx, model, scales, labels, reg_t, ctr_t, stats, inv_world, sel, *towers):
         head = model.head
         nl = len(towers) // 2
         cls_t, box_t = list(towers[:nl]), list(towers[nl:])
@@ -206,10 +210,10 @@ class _FcosHeadLossFn(torch.autograd.Function):
         else:
             ctr_ptr, ld_ctr = cls_buf.view(-1)[K:], head.kc_pad
         sums = HF.fcos_regctr_loss_fwd(box_buf, 8, ctr_ptr, ld_ctr, labels, reg_t, ctr_t, head.scales.detach(), N, hw,
-                                       head.fpn_strides, K, model.iou_loss_type, head.norm_reg_targets)
+                                       head.fpn_strides, K, model.iou_loss_type, head.norm_reg_targets, sel=sel)
         out3 = HF.fcos_finalize_losses(focal_sum, sums, stats, inv_world)
         ctx.model, ctx.hw, ctx.inv_world = model, hw, inv_world
-        ctx.save_for_backward(cls_buf, box_buf, labels, reg_t, ctr_t, stats, *towers)
+        ctx.save_for_backward(cls_buf, box_buf, labels, reg_t, ctr_t, stats, sel, *towers)
         arena = _arena_of(head)
         if arena is not None:
             for p in (head.cls_pred.weight, head.cls_pred.bias, head.box_pred.weight, head.box_pred.bias, head.scales):
@@ -224,8 +228,8 @@ class _FcosHeadLossFn(torch.autograd.Function):
     def backward(ctx, g_cls, g_reg, g_ctr):
         model, hw, inv_world = ctx.model, ctx.hw, ctx.inv_world
         head = model.head
-        cls_buf, box_buf, labels, reg_t, ctr_t, stats = ctx.saved_tensors[:6]
-        towers = ctx.saved_tensors[6:]
+        cls_buf, box_buf, labels, reg_t, ctr_t, stats, sel = ctx.saved_tensors[:7]
+        towers = ctx.saved_tensors[7:]
         nl = len(towers) // 2
         cls_t, box_t = towers[:nl], towers[nl:]
         g3 = [g.reshape(1).float() if g is not None else torch.zeros(1, dtype=torch.float32, device=cls_buf.device) for g in (g_cls, g_reg, g_ctr)]
@@ -245,7 +249,7 @@ class _FcosHeadLossFn(torch.autograd.Function):
             dctr, ld_dctr, dctr_col, ctr_col = dcls, kcp, K, 4
         HF.fcos_regctr_loss_bwd(box_buf, 8, ctr_ptr, ld_ctr, labels, reg_t, ctr_t, head.scales.detach(), N, hw, head.fpn_strides, K,
                                 model.iou_loss_type, head.norm_reg_targets, g3[1], g3[2], stats, inv_world,
-                                dbox, 8, ctr_col, dctr, ld_dctr, dctr_col, arena.grad_view(head.scales))
+                                dbox, 8, ctr_col, dctr, ld_dctr, dctr_col, arena.grad_view(head.scales), sel=sel)
         arena.mark_ready(head.scales)
         offs, off = [], 0
         for h, w in hw:
@@ -264,7 +268,7 @@ class _FcosHeadLossFn(torch.autograd.Function):
             dys = [dbuf.view(-1)[o * kk:] for o in offs]
             grads.append(HF.conv2d_dgrad_ml(dys, pred.wt_bf16, hw, 1, 1, 1, dy_img_stride=L * kk, N=N, k_real=kr))
         grads_cls, grads_box = grads
-        return (None, None, None, None, None, None, None, *grads_cls, *grads_box)
+        return (None, None, None, None, None, None, None, None, *grads_cls, *grads_box)
 
 
 @META_ARCH_REGISTRY.register()
@@ -352,7 +356,8 @@ class FCOSV2(nn.Module):
         level_hw = [((Hp + s - 1) // s, (Wp + s - 1) // s) for s in self.fpn_strides]
         if self.training:
             # targets first: they depend only on the ground truth, so the normaliser all-reduce overlaps the backbone
-            labels, reg_t, ctr_t, stats = self.get_ground_truth(level_hw, gt_instances)
+            labels, reg_t, ctr_t, stats, *sel = self.get_ground_truth(level_hw, gt_instances)     # FCOSTopK: + the selected rows
+            sel = sel[0] if sel else None
             world = comm.get_world_size()
             stats_work = None
             if comm.collectives_active():       # asynchronous: the compute stream only waits for it in front of the loss node, a whole forward pass later
@@ -366,16 +371,20 @@ class FCOSV2(nn.Module):
         if self.training:
             if stats_work is not None:
                 stats_work.wait()
-            l_cls, l_reg, l_ctr = _FcosHeadLossFn.apply(self, self.head.scales, labels, reg_t, ctr_t, stats, 1.0 / float(world), *cls_t, *box_t)
+            l_cls, l_reg, l_ctr = _FcosHeadLossFn.apply(self, self.head.scales, labels, reg_t, ctr_t, stats, 1.0 / float(world), sel, *cls_t, *box_t)
             return dict(cls_loss=l_cls, reg_loss=l_reg, centerness_loss=l_ctr)
         results = self.inference(level_hw, cls_t, box_t, images.image_sizes)
         return self.postprocess(results, batched_inputs, images.image_sizes)
 
     def losses(self, gt_classes, reg_targets, pred_class_logits, pred_box_reg, pred_center_score):
+        return self._losses(gt_classes, reg_targets, pred_class_logits, pred_box_reg, pred_center_score)
+
+    def _losses(self, gt_classes, reg_targets, pred_class_logits, pred_box_reg, pred_center_score, topk_locations=None):
         """FCOSV2.losses with the reference's argument contract (fcosv2.py:104-148): per-level NCHW prediction lists, labels
         (N, L) / (N*L,), regression targets (N, L, 4).  The training step does NOT come through here - forward() fuses the three
         losses with the prediction convs (_FcosHeadLossFn) - but code written against the reference's method keeps working, on the
-        same HIP loss kernels and with the normalisers kept on the device (the reference reads them back with .item())."""
+        same HIP loss kernels and with the normalisers kept on the device (the reference reads them back with .item()).
+        ``topk_locations`` (FCOSTopK.losses, fcos_topk.py:208-225): the rows of the regression loss and of its normaliser."""
         from ...layers.losses import bce_with_logits_fg_sum, iou_loss, sigmoid_focal_loss_jit
         from ...utils import comm
 
@@ -395,8 +404,9 @@ class FCOSV2(nn.Module):
         ctr_t = torch.sqrt((lr.min(-1)[0] / lr.max(-1)[0]).clamp(min=0) * (tb.min(-1)[0] / tb.max(-1)[0]).clamp(min=0))
         ctr_t = torch.where(fg, ctr_t, torch.zeros_like(ctr_t))
         if bool(fg.any()):
-            sum_ctr_avg = comm.reduce_sum(ctr_t.sum().reshape(1)) / world
-            reg_loss = iou_loss(reg[fg], reg_t[fg], ctr_t[fg], loss_type=self.iou_loss_type) / sum_ctr_avg[0]
+            rows = fg if topk_locations is None else topk_locations.reshape(-1).bool()
+            sum_ctr_avg = comm.reduce_sum(ctr_t[rows].sum().reshape(1)) / world
+            reg_loss = iou_loss(reg[rows], reg_t[rows], ctr_t[rows], loss_type=self.iou_loss_type) / sum_ctr_avg[0]
             centerness_loss = bce_with_logits_fg_sum(ctr, ctr_t, labels, K) / num_pos_avg[0]
         else:                 # fcosv2.py:143-146: keep the graph and the collective alive
             reg_loss = reg[fg].sum()
@@ -407,6 +417,12 @@ class FCOSV2(nn.Module):
     @torch.no_grad()
     def get_ground_truth(self, level_hw, gt_instances):
         """fcosv2.py:150-172 + fcos/utils.py:160-212 for the whole batch in one kernel."""
+        boxes, classes, offs = self._gt_tensors(gt_instances)
+        return HF.fcos_assign(boxes, classes, offs, len(gt_instances), level_hw, self.fpn_strides, SIZES_OF_INTEREST,
+                              self.center_sampling_radius, self.num_classes)
+
+    def _gt_tensors(self, gt_instances):
+        """Concatenated gt boxes (sumG, 4) fp32, classes (sumG,) int32 and per-image offsets (N + 1,) int32 on the device."""
         dev = self.device
         counts = [len(g) for g in gt_instances]
         offs = torch.tensor([0] + counts, dtype=torch.int64).cumsum(0).to(torch.int32).to(dev, non_blocking=True)
@@ -416,8 +432,7 @@ class FCOSV2(nn.Module):
         else:
             boxes = torch.zeros((1, 4), dtype=torch.float32, device=dev)
             classes = torch.zeros((1,), dtype=torch.int32, device=dev)
-        return HF.fcos_assign(boxes, classes, offs, len(gt_instances), level_hw, self.fpn_strides, SIZES_OF_INTEREST,
-                              self.center_sampling_radius, self.num_classes)
+        return boxes, classes, offs
 
     # ------------------------------------------------------------------ inference (fcosv2.py:174-266)
     @torch.no_grad()
@@ -481,6 +496,40 @@ class FCOSV2(nn.Module):
         imgs = [im if im.dtype == torch.uint8 else im.float() for im in imgs]
         HF.preprocess_batch(imgs, batch, self._mean, self._std)       # one launch for the batch
         return ImageList(batch, sizes)
+
+
+@META_ARCH_REGISTRY.register()
+class FCOSTopK(FCOSV2):
+    """slender_det/modeling/meta_arch/fcos/fcos_topk.py:102-468 (configs/fcos/fcos_topk_R_50_FPN_1x.yaml).  FCOSV2 whose box
+    regression is supervised only at the ``topk_per_box`` (5, hard-coded at :39) most central positive locations of every gt box
+    (:78-91); classification and centerness keep all positives (:204-207, :227-229).  The regression loss is normalised by the sum
+    of centerness targets over the selected rows (:211-215).  Head, inference and post-processing are FCOSV2's (:261-336, :364-468).
+
+    The reference finds the selection in a Python loop over images x gts with one host read per gt; here it comes out of the
+    assignment launch (``sod_fcos_assign_topk``), with the ties that ``torch.topk(sorted=False)`` leaves open resolved as: higher
+    centerness first, then lower location index.  The targets are in pixels also under NORM_REG_TARGETS (:255-258 never passes the
+    flag on), which is what the assignment kernel produces.  An image without gt is all background with nothing selected (the
+    reference raises on it)."""
+    topk_per_box = 5
+
+    def __init__(self, cfg):
+        super().__init__(cfg)
+        self.last_topk = None       # (N, L) uint8 selection of the last training step, for inspection
+
+    def losses(self, gt_classes, reg_targets, pred_class_logits, pred_box_reg, pred_center_score, topk_locations):
+        """FCOSTopK.losses with the reference's argument contract (fcos_topk.py:184-235); see ``FCOSV2.losses``."""
+        return self._losses(gt_classes, reg_targets, pred_class_logits, pred_box_reg, pred_center_score, topk_locations)
+
+    @torch.no_grad()
+    def get_ground_truth(self, level_hw, gt_instances):
+        """fcos_topk.py:237-259 + :24-101 for the whole batch: -> labels, reg_targets, ctr_targets, stats (3,) = [num_pos, sum of
+        centerness over the selected rows, the same over all foreground rows], sel (N, L) uint8.  No host read."""
+        boxes, classes, offs = self._gt_tensors(gt_instances)
+        labels, reg_t, ctr_t, _gt_index, sel, stats = HF.fcos_assign_topk(
+            boxes, classes, offs, len(gt_instances), level_hw, self.fpn_strides, SIZES_OF_INTEREST, self.center_sampling_radius,
+            self.num_classes, self.topk_per_box)
+        self.last_topk = sel
+        return labels, reg_t, ctr_t, stats, sel
 
 
 @META_ARCH_REGISTRY.register()

@@ -13,7 +13,8 @@ anchor-match kernel, and the one-node loss function.  Differences that are repro
   * refine labels come from MaxIoU(pos 0.5, neg 0.4, gt_max_matching) on init boxes clamped to >= 0 (:415-470): the 0.4-0.5 band
     is background, not ignored; nothing is masked by the image size;
   * normalisers are the per-batch positive counts (:301-312), no EMA.
-``LRTBHead`` / ``LRTBTopkHead`` / ``AnchorHead`` are not built yet.
+``LRTBHead`` / ``LRTBTopkHead`` (meta/heads/lrtb_head.py, lrtb_topk_head.py) and ``AnchorHead`` (meta/heads/anchor_head.py) follow below on
+the same machinery.
 """
 import math
 
