@@ -436,12 +436,15 @@ int sod_nms_rotated(const float* boxes, const long long* order, int n, float iou
 int sod_box_iou_rotated(const float* boxes1, int n1, const float* boxes2, int n2, float* iou_out, void* stream);
 /* detectron2 ROIAlign(output_size, spatial_scale, sampling_ratio, aligned=True) / ROIAlignRotated (roi_heads/roi_heads.py:48-53).
  * x: NHWC bf16; rois (R,5) [batch,x1,y1,x2,y2] or, rotated, (R,6) [batch,cx,cy,w,h,angle_deg]; out (R,PH,PW,C) fp32.
- * bwd accumulates atomically into dx (N,H,W,C) fp32 (zero it first). */
+ * bwd accumulates atomically into dx (N,H,W,C) fp32 (zero it first).  R = 0 is a no-op (rois may then be NULL: an empty tensor has no storage). */
 int sod_roi_align_fwd(const void* x, const float* rois, float* out, int R, int N, int H, int W, int C, int PH, int PW,
                       float spatial_scale, int sampling_ratio, int rotated, void* stream);
 /* the same with fp32 features (fp32 validation mode of the two-stage path; the backward already works on fp32 rows) */
 int sod_roi_align_fwd_f32(const float* x, const float* rois, float* out, int R, int N, int H, int W, int C, int PH, int PW,
                           float spatial_scale, int sampling_ratio, int rotated, void* stream);
+/* bwd: C % 32 == 0 accumulates in fixed point in LDS tiles with max|dout| * 2^-F steps per (roi, 32-channel chunk): F = 24 up to
+ * PH * PW = 64 bins, 29 - ceil(log2(PH * PW)) beyond, so that the per-pixel sum fits in 31 bits for every output size; PH * PW > 1024,
+ * sampling_ratio > 1024 and every other C take the per-sample fp32 atomics instead. */
 int sod_roi_align_bwd(const float* dout, const float* rois, float* dx, int R, int N, int H, int W, int C, int PH, int PW,
                       float spatial_scale, int sampling_ratio, int rotated, void* stream);
 /* fvcore.nn.giou_loss(boxes1, boxes2, eps) on XYXY (retina_rotated.py:240): per-row loss, optional sum, optional gradient

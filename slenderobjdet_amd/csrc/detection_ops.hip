@@ -451,9 +451,25 @@ __global__ __launch_bounds__(256) void roi_align_kernel(const RoiArgs a, float* 
 
 // Tiled ROIAlign backward: one workgroup per (roi, 32-channel chunk) accumulates dX for the roi's footprint in 16x16-pixel LDS
 // tiles in fixed point (ds_add_u32, see deform_conv.hip for the measurement behind that choice) and flushes each tile with one
-// global atomic per touched element, instead of 4 corners x samples x channels global atomics per bin.  Scale: an element
-// receives at most sum_bins |g_bin| <= 64 * max|g| (the bilinear weights of a bin's samples, divided by the sample count, sum to
-// <= 1), so 2^(24 - ex) with max|g| < 2^ex cannot overflow 31 bits.
+// global atomic per touched element, instead of 4 corners x samples x channels global atomics per bin.
+// Scale: with max|g| < 2^ex over the (roi, chunk), an addend is v = g * 2^(F - ex) / count * w.  The bilinear weights of one bin's
+// samples, divided by the sample count, sum to <= 1, so one bin sends a pixel sum|v| <= 2^F (1 + a few ulp) and the nb = PH * PW
+// bins together <= nb * 2^F: the per-pixel sum is bounded by the NUMBER OF BINS (a sub-pixel ROI clamped onto a corner pixel sends
+// every bin there), not by a constant.  F = roi_bwd_frac_bits(nb) keeps the sum of the ROUNDED addends inside 31 bits:
+//   nb <= 64: F = 24.  sum|rn(v)| <= sum|v| + A / 2 <= 2^30 (1 + a few ulp) + A / 2 for A non-zero addends at the pixel.  A sample
+//             reaches a pixel only from its 2x2 support (3x3 with the clamp band of a border pixel); with the adaptive ratio the
+//             samples of one axis are > 0.5 px apart (or there is one per bin), with a fixed one A <= 4 nb sr^2 and the entry point
+//             keeps sr <= ROI_TILE_MAX_SR: A / 2 < 2^29 either way.
+//   nb >  64: F = 29 - ceil(log2 nb).  |rn(v)| <= 2|v| for every v, so sum|rn(v)| <= 2 nb 2^F (1 + a few ulp) <= 2^30 (1 + ...).
+// Every addend is rounded to nearest: the error per addend is at most half a step, 2^(ex - F - 1) <= max|g| * 2^-F.
+// Output sizes beyond ROI_TILE_MAX_BINS (F would drop below 19 bits) take the generic kernel (sod_roi_align_bwd).
+constexpr int ROI_TILE_MAX_BINS = 1024, ROI_TILE_MAX_SR = 1024;
+__host__ __device__ inline int roi_bwd_frac_bits(int nb) {
+  if (nb <= 64) return 24;
+  int lg = 0;
+  while ((1 << lg) < nb) ++lg;
+  return 29 - lg;
+}
 constexpr int ROI_T = 16;    // tile edge (pixels)
 constexpr int ROI_CC = 32;   // channels per workgroup
 __global__ __launch_bounds__(256) void roi_align_bwd_tile_kernel(const RoiArgs a, const float* __restrict__ dout, float* __restrict__ dx) {
@@ -503,7 +519,8 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tile_kernel(const RoiArgs a
   if (gmax == 0.f || !(gmax < 3.0e38f)) return;   // nothing to add / non-finite gradient (the loss is already non-finite then)
   int ex = 0;
   (void)frexpf(gmax, &ex);
-  const float S = ldexpf(1.f, 24 - ex) / count, invS = ldexpf(1.f, ex - 24);
+  const int F = roi_bwd_frac_bits(nb);
+  const float S = ldexpf(1.f, F - ex) / count, invS = ldexpf(1.f, ex - F);
   const long long base = ((long long)b * a.H) * a.W;
   for (int ty = wy0; ty <= wy1; ty += ROI_T)
     for (int tx = wx0; tx <= wx1; tx += ROI_T) {
@@ -989,7 +1006,7 @@ extern "C" int sod_box_iou_rotated(const float* boxes1, int n1, const float* box
 
 static int roi_fill(RoiArgs& a, const void* x, const float* rois, int R, int N, int H, int W, int C, int PH, int PW, float scale,
                     int sampling_ratio, int rotated) {
-  if (!x || !rois || R < 0 || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || PH <= 0 || PW <= 0) return SOD_EARG;
+  if (!x || (!rois && R > 0) || R < 0 || N <= 0 || H <= 0 || W <= 0 || C <= 0 || (C & 7) || PH <= 0 || PW <= 0) return SOD_EARG;
   a.x = (const __bf16*)x; a.rois = rois; a.R = R; a.N = N; a.H = H; a.W = W; a.C = C; a.PH = PH; a.PW = PW;
   a.scale = scale; a.sampling_ratio = sampling_ratio; a.rotated = rotated;
   return SOD_OK;
@@ -999,8 +1016,9 @@ extern "C" int sod_roi_align_fwd(const void* x, const float* rois, float* out, i
                                  float spatial_scale, int sampling_ratio, int rotated, void* stream) {
   RoiArgs a{};
   int rc = roi_fill(a, x, rois, R, N, H, W, C, PH, PW, spatial_scale, sampling_ratio, rotated);
-  if (rc || !out) return rc ? rc : SOD_EARG;
-  if (R == 0) return SOD_OK;
+  if (rc) return rc;
+  if (R == 0) return SOD_OK;      // nothing to do: rois and out of an empty call may be NULL
+  if (!out) return SOD_EARG;
   SOD_LAUNCH((roi_align_kernel<false, false>), dim3(nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -1010,8 +1028,9 @@ extern "C" int sod_roi_align_fwd_f32(const float* x, const float* rois, float* o
                                      float spatial_scale, int sampling_ratio, int rotated, void* stream) {
   RoiArgs a{};
   int rc = roi_fill(a, x, rois, R, N, H, W, C, PH, PW, spatial_scale, sampling_ratio, rotated);
-  if (rc || !out) return rc ? rc : SOD_EARG;
-  if (R == 0) return SOD_OK;
+  if (rc) return rc;
+  if (R == 0) return SOD_OK;      // nothing to do: rois and out of an empty call may be NULL
+  if (!out) return SOD_EARG;
   SOD_LAUNCH((roi_align_kernel<false, true>), dim3(nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -1021,9 +1040,11 @@ extern "C" int sod_roi_align_bwd(const float* dout, const float* rois, float* dx
                                  float spatial_scale, int sampling_ratio, int rotated, void* stream) {
   RoiArgs a{};
   int rc = roi_fill(a, dx, rois, R, N, H, W, C, PH, PW, spatial_scale, sampling_ratio, rotated);   // x unused in bwd
-  if (rc || !dout || !dx) return rc ? rc : SOD_EARG;
+  if (rc) return rc;
   if (R == 0) return SOD_OK;
-  if (C % ROI_CC == 0 && C / ROI_CC <= 65535) {
+  if (!dout) return SOD_EARG;
+  // the tiles' fixed point is proven for these output sizes and sampling ratios only (see roi_align_bwd_tile_kernel)
+  if (C % ROI_CC == 0 && C / ROI_CC <= 65535 && (long long)PH * PW <= ROI_TILE_MAX_BINS && sampling_ratio <= ROI_TILE_MAX_SR) {
     SOD_LAUNCH(roi_align_bwd_tile_kernel, dim3(R, C / ROI_CC), dim3(256), 0, (hipStream_t)stream, a, dout, dx);
     SOD_CHECK_LAUNCH();
     return SOD_OK;
