@@ -5,7 +5,7 @@
 //   fcos_decode_kernel      one workgroup per (image, level): sigmoid -> threshold -> x sigmoid(centerness) -> per-level top-k (exact
 //                           radix select over the score bits) -> decode l/t/r/b into boxes -> sqrt; candidates come out in the order
 //                           torch's nonzero() gives them (location-major, class-minor), padded to top_n slots per level.
-//   (the batched class-aware NMS that consumes these candidates lives in detection_ops.hip: sod_batched_nms_*)
+//   (the batched class-aware NMS that consumes these candidates lives in nms.hip: sod_batched_nms_*)
 // The reference does all of this per image and per level with boolean indexing, .nonzero(), .item() and topk (one host sync each).
 #include "common.h"
 #include "../../include/slender_hip.h"

@@ -1,4 +1,4 @@
-// Rotated-box IoU as device code, shared by detection_ops.hip (NMS, anchor labelling, pairwise IoU) and coco_eval_rotated.hip.
+// Rotated-box IoU as device code, shared by nms.hip, detection_ops.hip (anchor labelling, pairwise IoU) and coco_eval_rotated.hip.
 // The including file places this header inside its own anonymous namespace (after common.h); the library is built with
 // -ffp-contract=off, so every translation unit gets the same bits out of these functions.
 #pragma once

@@ -1016,20 +1016,23 @@ def fcos_finalize_losses(focal_sum, regctr_sums, stats, inv_world):
 
 
 # ----------------------------------------------------------------------------------------------- detection ops
-def nms(boxes, scores, iou_threshold):
-    """torchvision.ops.nms contract: kept indices (int64) in descending-score order. Sorting is torch's stable sort (plumbing);
-    the IoU mask and the greedy scan run in the HIP kernels."""
+def _nms_single(symbol, boxes, scores, iou_threshold):
     _chk(boxes, torch.float32, "boxes"); _chk(scores, torch.float32, "scores")
-    n = boxes.shape[0]
-    dev = boxes.device
+    n, dev = boxes.shape[0], boxes.device
     if n == 0:
         return torch.empty((0,), dtype=torch.int64, device=dev)
     order = torch.sort(scores, descending=True, stable=True).indices.contiguous()
     keep = torch.empty(n, dtype=torch.int64, device=dev)
     nkeep = torch.zeros(1, dtype=torch.int32, device=dev)
     ws = torch.empty(int(_C.load().sod_nms_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-    call("sod_nms", ptr(boxes), ptr(order), n, float(iou_threshold), ptr(keep), ptr(nkeep), ptr(ws), stream_ptr())
+    call(symbol, ptr(boxes), ptr(order), n, float(iou_threshold), ptr(keep), ptr(nkeep), ptr(ws), stream_ptr())
     return keep[: int(nkeep.item())]
+
+
+def nms(boxes, scores, iou_threshold):
+    """torchvision.ops.nms contract: kept indices (int64) in descending-score order. Sorting is torch's stable sort (plumbing);
+    the IoU mask and the greedy scan run in the HIP kernels."""
+    return _nms_single("sod_nms", boxes, scores, iou_threshold)
 
 
 def fcos_decode(cls_buf, box_buf, scales, level_hw, strides, num_classes, centerness_on_reg, norm_reg_targets, pre_nms_thresh, pre_nms_top_n):
@@ -1104,16 +1107,7 @@ def rpn_clip_filter(boxes, scores, image_hw, min_size):
 
 def nms_rotated(boxes, scores, iou_threshold):
     """detectron2.layers.nms_rotated: boxes (n,5) = (cx,cy,w,h,angle_deg)."""
-    _chk(boxes, torch.float32, "boxes"); _chk(scores, torch.float32, "scores")
-    n, dev = boxes.shape[0], boxes.device
-    if n == 0:
-        return torch.empty((0,), dtype=torch.int64, device=dev)
-    order = torch.sort(scores, descending=True, stable=True).indices.contiguous()
-    keep = torch.empty(n, dtype=torch.int64, device=dev)
-    nkeep = torch.zeros(1, dtype=torch.int32, device=dev)
-    ws = torch.empty(int(_C.load().sod_nms_workspace_bytes(n)), dtype=torch.uint8, device=dev)
-    call("sod_nms_rotated", ptr(boxes), ptr(order), n, float(iou_threshold), ptr(keep), ptr(nkeep), ptr(ws), stream_ptr())
-    return keep[: int(nkeep.item())]
+    return _nms_single("sod_nms_rotated", boxes, scores, iou_threshold)
 
 
 def box_iou_rotated(b1, b2):

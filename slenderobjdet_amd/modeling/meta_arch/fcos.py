@@ -30,6 +30,7 @@ from ...layers.nn import ConvGnRelu, HipConv2d, HipGroupNorm, _arena_of, group_n
 from ...structures import Boxes, ImageList, Instances
 from ...utils import comm
 from ..backbone import build_backbone
+from ..postprocessing import batched_nms_instances, detector_postprocess
 from ..shape_spec import ShapeSpec
 from .build import META_ARCH_REGISTRY
 
@@ -449,27 +450,13 @@ class FCOSV2(nn.Module):
         """batched_nms + top-``max_detections_per_image`` (fcosv2.py:240-249) for all images on the device; the only host
         synchronisation of the whole post-processing is the final read of the per-image detection counts."""
         boxes, scores, classes, _counts = cand
-        keep, nkeep = HF.batched_nms_topk(boxes, scores, classes, self.nms_thresh, self.max_detections_per_image)
-        kb = torch.gather(boxes, 1, keep[:, :, None].expand(-1, -1, 4))
-        ks = torch.gather(scores, 1, keep)
-        kc = torch.gather(classes, 1, keep)
-        nk = nkeep.cpu().tolist()
-        results = []
-        for i, image_size in enumerate(image_sizes):
-            r = Instances(tuple(image_size))
-            r.pred_boxes = Boxes(kb[i, : nk[i]])
-            r.scores = ks[i, : nk[i]]
-            r.pred_classes = kc[i, : nk[i]].long()
-            results.append(r)
-        return results
+        return batched_nms_instances(boxes, scores, classes, self.nms_thresh, self.max_detections_per_image, image_sizes)
 
     @torch.no_grad()
     def inference(self, level_hw, cls_t, box_t, image_sizes):
         return self.nms_candidates(self.decode_candidates(cls_t, box_t), image_sizes)
 
     def postprocess(self, instances, batched_inputs, image_sizes):
-        from ..postprocessing import detector_postprocess
-
         out = []
         for res, inp, size in zip(instances, batched_inputs, image_sizes):
             h, w = inp.get("height", size[0]), inp.get("width", size[1])

@@ -21,8 +21,8 @@ from torch.autograd.function import once_differentiable
 from ...layers import functional as HF
 from ...layers.deform_conv import DeformConv
 from ...layers.nn import ConvGnRelu, ConvML, HipConv2d, _arena_of
-from ...structures import Boxes, Instances
 from ..backbone import build_backbone
+from ..postprocessing import batched_nms_instances
 from .build import META_ARCH_REGISTRY
 from .fcos import FCOSV2
 
@@ -340,17 +340,5 @@ class RepPointsDetector(nn.Module):
         valid = torch.isfinite(scores)[:, :, None]
         boxes = torch.where(valid, torch.gather(refine_boxes.float(), 1, grow[:, :, None].expand(-1, -1, 4)), torch.zeros((), device=rows.device)).contiguous()
         init = torch.gather(init_boxes.float(), 1, grow[:, :, None].expand(-1, -1, 4))
-        keep, nkeep = HF.batched_nms_topk(boxes, scores, classes, self.nms_threshold, self.max_detections_per_image)
-        kb = torch.gather(boxes, 1, keep[:, :, None].expand(-1, -1, 4))
-        ki = torch.gather(init, 1, keep[:, :, None].expand(-1, -1, 4))
-        ks, kc = torch.gather(scores, 1, keep), torch.gather(classes, 1, keep)
-        nk = nkeep.cpu().tolist()
-        results = []
-        for i, image_size in enumerate(image_sizes):
-            r = Instances(tuple(image_size))
-            r.pred_boxes = Boxes(kb[i, : nk[i]])
-            r.scores = ks[i, : nk[i]]
-            r.pred_classes = kc[i, : nk[i]].long()
-            r.init_boxes = ki[i, : nk[i]]
-            results.append(r)
-        return results
+        return batched_nms_instances(boxes, scores, classes, self.nms_threshold, self.max_detections_per_image, image_sizes,
+                                     extra={"init_boxes": init})

@@ -22,6 +22,7 @@ from ...layers.nn import ConvReluML, HipConv2d, _arena_of
 from ...structures import ImageList
 from ..anchor_generator import grid_anchors
 from ..backbone import build_backbone
+from ..postprocessing import batched_nms_instances
 from .build import META_ARCH_REGISTRY
 from .fcos import FCOSV2
 
@@ -257,7 +258,6 @@ class RetinaNet(nn.Module):
         """retina_rotated.py:296-377 for the whole batch on the device: per level sigmoid over (HWA x K), top-k, score threshold
         (one selection launch), decode the surviving anchors (Box2BoxTransform.apply_deltas, one kernel), class-aware NMS and
         the top detections (batched NMS); the only host read is the final per-image detection count."""
-        from ...structures import Boxes, Instances
         from ..box_regression import Box2BoxTransform
 
         A, K = self.head.num_anchors, self.num_classes
@@ -275,15 +275,6 @@ class RetinaNet(nn.Module):
         sel_a = anchors[grow.reshape(-1)].contiguous()
         boxes = transform.apply_deltas(sel_d, sel_a).view(N, -1, 4)
         boxes = torch.where(torch.isfinite(scores)[:, :, None], boxes, torch.zeros_like(boxes)).contiguous()       # empty slots
-        keep, nkeep = HF.batched_nms_topk(boxes, scores, classes, self.nms_threshold, self.max_detections_per_image)
-        kb = torch.gather(boxes, 1, keep[:, :, None].expand(-1, -1, 4))
-        ks, kc = torch.gather(scores, 1, keep), torch.gather(classes, 1, keep)
-        nk = nkeep.cpu().tolist()
-        results = []
-        for i, image_size in enumerate(image_sizes):
-            r = Instances(tuple(image_size))
-            r.pred_boxes, r.scores, r.pred_classes = Boxes(kb[i, : nk[i]]), ks[i, : nk[i]], kc[i, : nk[i]].long()
-            results.append(r)
-        return results
+        return batched_nms_instances(boxes, scores, classes, self.nms_threshold, self.max_detections_per_image, image_sizes)
 
     postprocess = FCOSV2.postprocess

@@ -130,9 +130,27 @@ def test_box_iou_rotated_known_values_and_oracle(cuda):
     assert (got - ref).abs().max() < 2e-4        # fp32 sin/cos and clipping order differ in the last ulps
 
 
-def test_nms_rotated_keep_indices(cuda):
+def _rboxes_clustered(n, seed):
+    """Jittered copies of 8 slender boxes, all centres inside a 60 x 60 px square: every 64 x 64 block of pairs holds far more than
+    64 pairs that pass the circle test, and many of them overlap above any threshold."""
+    g = _g(seed)
+    proto = torch.cat([300 + 8 + torch.rand(8, 2, generator=g) * 44, torch.rand(8, 1, generator=g) * 30 + 30, torch.rand(8, 1, generator=g) * 12 + 8,
+                       (torch.rand(8, 1, generator=g) - 0.5) * 180], 1)
+    b = proto[torch.arange(n) % 8]
+    b[:, :2] += (torch.rand(n, 2, generator=g) - 0.5) * 8
+    b[:, 2:4] *= 0.85 + torch.rand(n, 2, generator=g) * 0.3
+    b[:, 4] += (torch.rand(n, generator=g) - 0.5) * 12
+    b[[20, 90, 150], 3] = torch.tensor([0.5, 0.9, 0.25])      # a side below 1 px: these pairs bypass the prefilter
+    return b
+
+
+@pytest.mark.parametrize("thr", [0.3, 0.5, 0.7])
+@pytest.mark.parametrize("boxset", ["spread", "clustered"])
+def test_nms_rotated_keep_indices(cuda, boxset, thr):
     """Greedy rotated NMS: keep indices bit-exact w.r.t. the oracle's greedy scan over the SAME IoU matrix (the IoU values
-    themselves are checked against the oracle above to 2e-4; with 90k pairs some always sit within float noise of any threshold)."""
+    themselves are checked against the oracle above to 2e-4; with 90k pairs some always sit within float noise of any threshold).
+    The clustered set (seed 3: the CPU oracle's greedy scan keeps 15 / 25 / 67 of its 200 boxes at 0.3 / 0.5 / 0.7) sends far more
+    than 64 pairs of one block through the prefilter and the compaction of the mask kernel."""
     import numpy as np
 
     from slenderobjdet_amd.layers import functional as HF
@@ -149,11 +167,16 @@ def test_nms_rotated_keep_indices(cuda):
             dead[rest[iou[i, rest] > np.float32(thr)]] = True
         return torch.tensor(keep, dtype=torch.int64)
 
-    b, s = _rboxes(300, 3), torch.rand(300, generator=_g(4))
+    if boxset == "spread":
+        b, s = _rboxes(300, 3), torch.rand(300, generator=_g(4))
+    else:
+        b, s = _rboxes_clustered(200, 3), torch.rand(200, generator=_g(4))
     b[5] = b[2]
     s[9] = s[4]
     iou = HF.box_iou_rotated(b.to(cuda), b.to(cuda)).cpu().numpy()
-    assert torch.equal(HF.nms_rotated(b.to(cuda), s.to(cuda), 0.5).cpu(), greedy(iou, s, 0.5))
+    assert torch.equal(HF.nms_rotated(b.to(cuda), s.to(cuda), thr).cpu(), greedy(iou, s, thr))
+    if boxset != "spread" or thr != 0.5:
+        return
     idx = torch.randint(0, 3, (300,), generator=_g(5))
     keep = batched_nms_rotated(b.to(cuda), s.to(cuda), idx.to(cuda), 0.5).cpu()
     ref = []
@@ -163,6 +186,19 @@ def test_nms_rotated_keep_indices(cuda):
     # class offsets shift the centres by thousands of pixels, which perturbs the clipped polygon in the last float digits:
     # allow a pair sitting exactly at the threshold to flip
     assert len(set(keep.tolist()) ^ set(ref)) <= 2
+
+
+@pytest.mark.parametrize("n", [1, 64, 65, 130])
+@pytest.mark.parametrize("box_dim", [4, 5])
+def test_nms_single_equals_batched_of_one(cuda, box_dim, n):
+    """The single-image calls run the batched kernels with B = 1; class 0 shifts nothing, so both see bit-identical boxes."""
+    from slenderobjdet_amd.layers import functional as HF
+
+    b = (_boxes(n, n) if box_dim == 4 else _rboxes(n, n)).to(cuda)
+    s = torch.rand(n, generator=_g(n + 1)).to(cuda)
+    single = (HF.nms if box_dim == 4 else HF.nms_rotated)(b, s, 0.5)
+    keep, nkeep = HF.batched_nms_topk(b[None].contiguous(), s[None].contiguous(), torch.zeros((1, n), dtype=torch.int32, device=cuda), 0.5, n)
+    assert torch.equal(keep[0, : int(nkeep[0])], single)
 
 
 def test_anchor_match_full_size_bit_exact(cuda):
