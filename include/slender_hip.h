@@ -364,6 +364,16 @@ int sod_fcos_assign_topk(const float* boxes, const int* classes, const int* box_
                          const float* lvl_lo, const float* lvl_hi, float radius, int num_classes, int topk,
                          int* labels, float* reg_targets, float* ctr_targets, int* gt_index, unsigned char* sel,
                          float* stats3, float* ws, void* stream);
+/* FCOSRepPoints stage-1 targets (slender_det/modeling/meta_arch/fcos/fcos_rpd_s1_topk.py:25-134): sod_fcos_assign_topk whose
+ * centerness - the value written to ctr_targets, the score that ranks a box's positives and the addend of stats3[1], stats3[2] - is
+ * pow(c, r) with c = (min(l,r)/max(l,r)) * (min(t,b)/max(t,b)) (NO square root) and r = min(q, 1/q), q = (l+r)/(t+b) (:25-54), powf
+ * of the device libm.  labels, reg_targets, gt_index, the tie rule, the order of the partial sums, the empty image and the topk range
+ * are sod_fcos_assign_topk's (the same kernels, one template parameter). */
+int sod_fcos_assign_topk_slender(const float* boxes, const int* classes, const int* box_offsets, int N,
+                                 int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
+                                 const float* lvl_lo, const float* lvl_hi, float radius, int num_classes, int topk,
+                                 int* labels, float* reg_targets, float* ctr_targets, int* gt_index, unsigned char* sel,
+                                 float* stats3, float* ws, void* stream);
 /* FCOSTopK.losses, regression + centerness part (fcos_topk.py:208-229): sod_fcos_regctr_loss_fwd / _bwd / _bwd_f32 whose IoU
  * term, box gradient and d(scales) run only on rows with sel != 0 (:222-225); the centerness BCE term and its gradient stay on
  * all foreground rows (:227-229).  norm[1] is the sum of centerness targets over the selected rows (:211-215). */
@@ -406,6 +416,13 @@ int sod_fcos_decode(const float* cls_logits, int ld_cls, const float* box_raw, i
                     int N, int nlev, const int* H, const int* W, const int* strides, int num_classes,
                     int ctr_col_box, int ctr_col_cls, int norm_reg_targets, float pre_nms_thresh, int pre_nms_top_n,
                     float* out_boxes, float* out_scores, int* out_classes, int* out_counts, void* stream);
+/* sod_fcos_decode for FCOSRepPoints.inference_single_image (fcos_rpd_s1_topk.py:422-462): the first four columns of ltrb (N, L, ld_box)
+ * are the distances themselves - no exp, no Scale, no stride: boxes = (x - l, y - t, x + r, y + b), negative distances included.  The
+ * centerness logit of location (n, loc) is ctr_logits[(n * L + loc) * ld_ctr].  Candidate set, tie rule, slot order, sqrt and counts
+ * are sod_fcos_decode's (one kernel). */
+int sod_fcos_decode_ltrb(const float* cls_logits, int ld_cls, const float* ltrb, int ld_box, const float* ctr_logits, int ld_ctr,
+                         int N, int nlev, const int* H, const int* W, const int* strides, int num_classes, float pre_nms_thresh,
+                         int pre_nms_top_n, float* out_boxes, float* out_scores, int* out_classes, int* out_counts, void* stream);
 /* The same selection for heads without a centerness branch: rows of K class logits (RetinaNet: anchors, retina_rotated.py:296-340;
  * RepPoints: points, rpd.py:717-765), logits (N, R, ld) with R = sum rows[l] (level-major).  by_row_max = 0: candidates are the
  * (row, class) pairs with sigmoid(logit) > score_thresh, the top_n best per (image, level) are kept (= sort, take top_n, threshold);
@@ -643,6 +660,49 @@ int sod_reppoints_box_loss_bwd(const float* pred, const float* target, const int
                                float* dpred, void* stream);
 int sod_reppoints_finalize(const float* focal_sum, const float* init_sums2, const float* refine_sums2, float* normalizer,
                            float momentum, int num_images, float init_weight, float* out3, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
+ * FCOSRepPoints (slender_det/modeling/meta_arch/fcos/fcos_rpd_s1_topk.py:137-746), L = sum of level pixels, FCOS locations
+ * x = j * stride + stride / 2.  (Its stage-1 targets are sod_fcos_assign_topk_slender, its inference decode sod_fcos_decode_ltrb.)
+ * sod_level_scale_*: Scale (:639, :660) on fp32 rows, the scalar read from the device: y = x * scale[0];
+ *   bwd: dx = dy * scale[0], dscale[0] += sum(dy * x), block partials added in index order (ws: sod_reduce_workspace_bytes()).
+ * sod_points2ltrb_fwd: offsets2ltrb (:709-745) + the decode of forward (:222-234) for one level.  pts (N, H*W, ld) fp32 rows of
+ *   num_points (x, y) pairs (+ add, as sod_points2bbox_fwd); ltrb = (-min x, -min y, max x, max y) of the points times point_stride;
+ *   boxes (optional) = (cx - l, cy - t, cx + r, cy + b) with cx = w * loc_stride + loc_stride / 2; argidx = the four arg-point indices
+ *   in the packing of sod_points2bbox_fwd (byte c: distance c); of equal extrema the lowest point index wins.  ltrb / boxes are level
+ *   slices of (N, L, 4) buffers (out_img_stride floats between images, 0: dense), argidx of (N, L).
+ * sod_points2ltrb_bwd: whole rows of d(pts) (fp32 and / or bf16; zeros outside the arg points): -point_stride * d(l), d(t) at the arg-min
+ *   x / y, +point_stride * d(r), d(b) at the arg-max x / y.
+ * sod_fcos_rpd_refine_targets: get_ground_truth (:343-374) for all N images in two launches, no host synchronisation and no G x L
+ *   matrix: pairwise_iou(gt boxes of image n, candidates[n]) + Matcher([thr_lo, thr_hi], [label_below, label_between, label_above],
+ *   allow_low_quality: every candidate that attains a gt's best IoU).  gt boxes / classes concatenated with box_offsets (N + 1) on the
+ *   device; total_gt / max_gt = their number in the batch / in the largest image, known to the host (max_gt <= 4096, the limit of
+ *   sod_anchor_match; an image with more is matched against its first max_gt boxes).  candidates (N, L, 4) XYXY, image_hw (N, 2) floats.
+ *   matched_vals, matches (index inside the image's gts), match_labels (N, L) are bit-identical to N calls of sod_anchor_match.
+ *   cls_labels (N, L): the matched gt's class, num_classes where match_labels == 0 (label -1 keeps the class, :356-357), -1 where
+ *   x >= image_w or y >= image_h; cls_labels_bg (optional): the same with -1 replaced by num_classes (the focal term has no valid mask,
+ *   :279-286); refine_ltrb (N, L, 4): the matched gt as distances from the location.  An image without gt: match_labels =
+ *   label_below, cls = num_classes (-1 outside), zeros elsewhere.  gt_best_ws: total_gt words.
+ * sod_fcos_rpd_finalize (:263-317): out8[0..4) = {cls_loss = focal / max(n_refine * inv_world, 1), reg_loss_init = iou / (stats3[1] *
+ *   inv_world) (0 when nothing is selected: the reference divides 0 by 0), reg_loss = smoothl1 / max(1, max(n_refine * inv_world, 1)),
+ *   centerness_loss = bce / max(stats3[0] * inv_world, 1)}; out8[4..7) = d(loss) / d(sum) of reg_loss_init, reg_loss and
+ *   centerness_loss (what their backward kernels are scaled by), out8[7] = 1.
+ * --------------------------------------------------------------------------------------------------------- */
+int sod_level_scale_fwd(const float* x, const float* scale, float* y, long long n, void* stream);
+int sod_level_scale_bwd(const float* dy, const float* x, const float* scale, float* dx, long long n, float* dscale, float* ws, void* stream);
+int sod_points2ltrb_fwd(const float* pts, const float* add, int ld, int N, int H, int W, int loc_stride, float point_stride,
+                        int num_points, float* ltrb, float* boxes, long long out_img_stride, unsigned* argidx, long long arg_img_stride,
+                        void* stream);
+int sod_points2ltrb_bwd(const float* dltrb, long long out_img_stride, const unsigned* argidx, long long arg_img_stride, int ld,
+                        int N, int H, int W, float point_stride, int num_points, float* dpts_f32, void* dpts_bf16, void* stream);
+int sod_fcos_rpd_refine_targets(const float* gt_boxes, const int* gt_classes, const int* box_offsets, int N, int total_gt, int max_gt,
+                                const float* candidates, const float* image_hw, int nlevels, const int* lvl_h, const int* lvl_w,
+                                const int* lvl_stride, int num_classes, float thr_lo, float thr_hi, int label_below,
+                                int label_between, int label_above, int allow_low_quality, float* matched_vals, int* matches,
+                                signed char* match_labels, int* cls_labels, int* cls_labels_bg, float* refine_ltrb,
+                                unsigned* gt_best_ws, void* stream);
+int sod_fcos_rpd_finalize(const float* focal_sum, const float* iou_sum, const float* smoothl1_sum, const float* bce_sum,
+                          const float* stats3, const float* n_refine, float inv_world, float* out8, void* stream);
 
 /* BBOX_REG_LOSS_TYPE "giou" of RetinaNet (retina_rotated.py:236-245) and AnchorHead (meta/heads/anchor_head.py:366-374): positives decode
  * their deltas against the anchor (Box2BoxTransform.apply_deltas) and take fvcore giou_loss (eps 1e-7) against the matched gt box

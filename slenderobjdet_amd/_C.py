@@ -78,12 +78,14 @@ _SIGS = {
     "sod_fcos_regctr_loss_bwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _F,
                                  _P, _I, _I, _P, _I, _I, _P, _P, _P],
     "sod_fcos_assign_topk": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sod_fcos_assign_topk_slender": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _P, _F, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
     "sod_fcos_regctr_loss_sel_fwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "sod_fcos_regctr_loss_sel_bwd": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _F,
                                      _P, _I, _I, _P, _I, _I, _P, _P, _P],
     "sod_fcos_finalize_losses": [_P, _P, _P, _F, _P, _P],
     "sod_nms_workspace_bytes": [_I],
     "sod_fcos_decode": [_P, _I, _P, _I, _P, _I, _I, _P, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P, _P, _P, _P],
+    "sod_fcos_decode_ltrb": [_P, _I, _P, _I, _P, _I, _I, _I, _P, _P, _P, _I, _F, _I, _P, _P, _P, _P, _P],
     "sod_dense_topk_select": [_P, _I, _I, _I, _P, _I, _I, _F, _I, _P, _P, _P, _P, _P],
     "sod_batched_nms_workspace_bytes": [_I, _I, _I],
     "sod_batched_nms_prepare": [_P, _P, _P, _I, _I, _I, _P, _P],
@@ -142,6 +144,12 @@ _SIGS = {
     "sod_reppoints_box_loss_fwd": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P],
     "sod_reppoints_box_loss_bwd": [_P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _F, _F, _P, _P],
     "sod_reppoints_finalize": [_P, _P, _P, _P, _F, _I, _F, _P, _P],
+    "sod_level_scale_fwd": [_P, _P, _P, _L, _P],
+    "sod_level_scale_bwd": [_P, _P, _P, _P, _L, _P, _P, _P],
+    "sod_points2ltrb_fwd": [_P, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _L, _P, _L, _P],
+    "sod_points2ltrb_bwd": [_P, _L, _P, _L, _I, _I, _I, _I, _F, _I, _P, _P, _P],
+    "sod_fcos_rpd_refine_targets": [_P, _P, _P, _I, _I, _I, _P, _P, _I, _P, _P, _P, _I, _F, _F, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "sod_fcos_rpd_finalize": [_P, _P, _P, _P, _P, _P, _F, _P, _P],
     "sod_conv2d_fwd_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _I, _P],
     "sod_conv2d_dgrad_f32": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _I, _P],
     "sod_conv2d_wgrad_f32": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _P],

@@ -62,6 +62,15 @@ __device__ __forceinline__ float block_sum_256(float v, float* red /* >=4 floats
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// detectron2 pairwise_iou of two XYXY boxes, as the matchers evaluate it (sod_anchor_match in detection_ops.hip and the batched
+// sod_fcos_rpd_refine_targets in fcos_rpd.hip give bit-identical values: one definition)
+__device__ __forceinline__ float pair_iou(const float* g, const float* a) {
+  const float w = fminf(g[2], a[2]) - fmaxf(g[0], a[0]), h = fminf(g[3], a[3]) - fmaxf(g[1], a[1]);
+  const float inter = fmaxf(w, 0.f) * fmaxf(h, 0.f);
+  const float ag = (g[2] - g[0]) * (g[3] - g[1]), aa = (a[2] - a[0]) * (a[3] - a[1]);
+  return inter > 0.f ? inter / (ag + aa - inter) : 0.f;
+}
+
 // Bijective XCD-aware remap of a 1-D block id (guide T1): consecutive logical ids land on one XCD.
 __device__ __forceinline__ uint32_t xcd_remap(uint32_t bid, uint32_t nblk) {
   const uint32_t q = nblk >> 3, r = nblk & 7, xcd = bid & 7;

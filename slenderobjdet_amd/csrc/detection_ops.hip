@@ -319,12 +319,7 @@ __global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict_
 // Matcher(thresholds=[lo,hi], labels=[l0,l1,l2], allow_low_quality_matches) over pairwise_iou(gt (G), anchors (A)) without the
 // G x A matrix: pass 1 = per-anchor max/argmax over gts + per-gt max over anchors (atomicMax on float bits, IoU >= 0);
 // pass 2 = thresholds + low-quality promotion (anchor ties with the per-gt best, as `Q == best_per_gt[:, None]`).
-__device__ __forceinline__ float pair_iou(const float* g, const float* a) {
-  const float w = fminf(g[2], a[2]) - fmaxf(g[0], a[0]), h = fminf(g[3], a[3]) - fmaxf(g[1], a[1]);
-  const float inter = fmaxf(w, 0.f) * fmaxf(h, 0.f);
-  const float ag = (g[2] - g[0]) * (g[3] - g[1]), aa = (a[2] - a[0]) * (a[3] - a[1]);
-  return inter > 0.f ? inter / (ag + aa - inter) : 0.f;
-}
+// (pair_iou, the XYXY IoU of pairwise_iou, lives in common.h: the batched matcher of fcos_rpd.hip must reproduce it bit for bit)
 
 // D = 4: XYXY boxes (pairwise_iou); D = 5: (cx, cy, w, h, angle) boxes (pairwise_iou_rotated, RRPN / RROIHeads)
 template <int D>

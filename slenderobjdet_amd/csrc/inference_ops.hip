@@ -18,11 +18,12 @@ constexpr int DEC_CHUNK = DEC_THREADS * DEC_V;
 
 struct DecodeArgs {
   const float* cls;       // (N, L, ld_cls) logits
-  const float* box;       // (N, L, ld_box) raw regression (+ centerness logit in column ctr_col_box when >= 0)
+  const float* box;       // (N, L, ld_box) raw regression, first 4 columns
   const float* scales;    // [nlev] Scale values (fcos.py:532)
   int N, L, nlev, K, ld_cls, ld_box;
-  int ctr_col_box, ctr_col_cls;
-  int norm_reg, top_n;
+  int norm_reg, top_n;     // norm_reg 0: exp(scale * x); 1: relu(scale * x) * stride; 2: x as it is (linear LTRB, FCOSRepPoints)
+  const float* ctr;       // mode 0: centerness logit of location (n, loc) = ctr[(n * L + loc) * ld_ctr] (a column of cls / box, or a buffer of its own)
+  int ld_ctr;
   float thresh;
   int H[SOD_MAX_LEVELS], W[SOD_MAX_LEVELS], stride[SOD_MAX_LEVELS], loc0[SOD_MAX_LEVELS];
   int mode;               // 0: FCOS (rows = locations, score x centerness, boxes decoded, sqrt)
@@ -76,9 +77,8 @@ __global__ __launch_bounds__(DEC_THREADS) void fcos_decode_kernel(const DecodeAr
     const int loc = (int)(e / K);
     return cls[(long long)loc * a.ld_cls + (int)(e - (long long)loc * K)];
   };
-  auto ctr_at = [&](int loc) -> float {
-    return a.ctr_col_box >= 0 ? box[(long long)loc * a.ld_box + a.ctr_col_box] : cls[(long long)loc * a.ld_cls + a.ctr_col_cls];
-  };
+  const float* ctr = a.ctr + ((long long)n * a.L + a.loc0[l]) * a.ld_ctr;
+  auto ctr_at = [&](int loc) -> float { return ctr[(long long)loc * a.ld_ctr]; };
   // candidate test and score key of element e (fcosv2.py:206-212: keep = sigmoid(cls) > thresh; score = sigmoid(cls) * sigmoid(ctr))
   auto key_of = [&](long long e, bool& cand) -> unsigned {
     if (a.mode == 2) {                   // rpd.py:741-748: scores, classes = logits.sigmoid().max(1); keep = score > threshold
@@ -142,7 +142,7 @@ __global__ __launch_bounds__(DEC_THREADS) void fcos_decode_kernel(const DecodeAr
 
   // ---- pass 3: ordered compaction + decode.  Selected = candidate with key > T, or key == T among the first `quota` such elements.
   const long long slot0 = ((long long)n * a.nlev + l) * a.top_n;
-  const float scale = a.mode == 0 ? a.scales[l] : 1.f;      // the generic modes have no Scale / box inputs
+  const float scale = (a.mode == 0 && a.norm_reg != 2) ? a.scales[l] : 1.f;      // the generic modes have no Scale / box inputs
   const int W = a.W[l], stride = a.stride[l];
   unsigned out_base = 0u, eq_seen = 0u;
   for (long long c0 = 0; c0 < total; c0 += DEC_CHUNK) {
@@ -192,7 +192,7 @@ __global__ __launch_bounds__(DEC_THREADS) void fcos_decode_kernel(const DecodeAr
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
           const float z = br[k] * scale;
-          r[k] = a.norm_reg ? fmaxf(z, 0.f) * (float)stride : expf(z);
+          r[k] = a.norm_reg == 2 ? br[k] : (a.norm_reg ? fmaxf(z, 0.f) * (float)stride : expf(z));
         }
         float* ob = a.out_boxes + (slot0 + pos) * 4;
         ob[0] = x - r[0]; ob[1] = y - r[1]; ob[2] = x + r[2]; ob[3] = y + r[3];
@@ -220,18 +220,18 @@ __global__ __launch_bounds__(DEC_THREADS) void fcos_decode_kernel(const DecodeAr
 
 }  // namespace
 
-extern "C" int sod_fcos_decode(const float* cls_logits, int ld_cls, const float* box_raw, int ld_box, const float* scales,
-                               int N, int nlev, const int* H, const int* W, const int* strides, int num_classes,
-                               int ctr_col_box, int ctr_col_cls, int norm_reg_targets, float pre_nms_thresh, int pre_nms_top_n,
-                               float* out_boxes, float* out_scores, int* out_classes, int* out_counts, void* stream) {
-  if (!cls_logits || !box_raw || !scales || !H || !W || !strides || !out_boxes || !out_scores || !out_classes || !out_counts) return SOD_EARG;
-  if (N <= 0 || nlev <= 0 || nlev > SOD_MAX_LEVELS || num_classes <= 0 || ld_cls < num_classes || ld_box < 4 || pre_nms_top_n <= 0) return SOD_EARG;
-  if ((ctr_col_box >= 0) == (ctr_col_cls >= 0) || ctr_col_box >= ld_box || ctr_col_cls >= ld_cls) return SOD_EARG;
+// reg_mode = DecodeArgs::norm_reg; ctr / ld_ctr = where the centerness logits live
+static int fcos_decode_impl(const float* cls_logits, int ld_cls, const float* box_raw, int ld_box, const float* scales, const float* ctr, int ld_ctr,
+                            int N, int nlev, const int* H, const int* W, const int* strides, int num_classes, int reg_mode,
+                            float pre_nms_thresh, int pre_nms_top_n, float* out_boxes, float* out_scores, int* out_classes, int* out_counts,
+                            void* stream) {
+  if (!cls_logits || !box_raw || !ctr || !H || !W || !strides || !out_boxes || !out_scores || !out_classes || !out_counts) return SOD_EARG;
+  if (N <= 0 || nlev <= 0 || nlev > SOD_MAX_LEVELS || num_classes <= 0 || ld_cls < num_classes || ld_box < 4 || ld_ctr < 1 || pre_nms_top_n <= 0) return SOD_EARG;
   if (pre_nms_top_n >= 65536) return SOD_EARG;       // packed 16-bit block counts
   DecodeArgs a{};
-  a.cls = cls_logits; a.box = box_raw; a.scales = scales;
+  a.cls = cls_logits; a.box = box_raw; a.scales = scales; a.ctr = ctr; a.ld_ctr = ld_ctr;
   a.N = N; a.nlev = nlev; a.K = num_classes; a.ld_cls = ld_cls; a.ld_box = ld_box;
-  a.ctr_col_box = ctr_col_box; a.ctr_col_cls = ctr_col_cls; a.norm_reg = norm_reg_targets; a.top_n = pre_nms_top_n; a.thresh = pre_nms_thresh;
+  a.norm_reg = reg_mode; a.top_n = pre_nms_top_n; a.thresh = pre_nms_thresh;
   long long L = 0;
   for (int l = 0; l < nlev; ++l) {
     if (H[l] <= 0 || W[l] <= 0 || strides[l] <= 0) return SOD_EARG;
@@ -247,6 +247,25 @@ extern "C" int sod_fcos_decode(const float* cls_logits, int ld_cls, const float*
   return SOD_OK;
 }
 
+extern "C" int sod_fcos_decode(const float* cls_logits, int ld_cls, const float* box_raw, int ld_box, const float* scales,
+                               int N, int nlev, const int* H, const int* W, const int* strides, int num_classes,
+                               int ctr_col_box, int ctr_col_cls, int norm_reg_targets, float pre_nms_thresh, int pre_nms_top_n,
+                               float* out_boxes, float* out_scores, int* out_classes, int* out_counts, void* stream) {
+  if (!cls_logits || !box_raw || !scales) return SOD_EARG;
+  if ((ctr_col_box >= 0) == (ctr_col_cls >= 0) || ctr_col_box >= ld_box || ctr_col_cls >= ld_cls) return SOD_EARG;
+  const float* ctr = ctr_col_box >= 0 ? box_raw + ctr_col_box : cls_logits + ctr_col_cls;
+  return fcos_decode_impl(cls_logits, ld_cls, box_raw, ld_box, scales, ctr, ctr_col_box >= 0 ? ld_box : ld_cls, N, nlev, H, W, strides, num_classes,
+                          norm_reg_targets ? 1 : 0, pre_nms_thresh, pre_nms_top_n, out_boxes, out_scores, out_classes, out_counts, stream);
+}
+
+// FCOSRepPoints.inference_single_image (fcos_rpd_s1_topk.py:422-462): the regression columns ARE the distances - no exp, no Scale, no stride
+extern "C" int sod_fcos_decode_ltrb(const float* cls_logits, int ld_cls, const float* ltrb, int ld_box, const float* ctr_logits, int ld_ctr,
+                                    int N, int nlev, const int* H, const int* W, const int* strides, int num_classes, float pre_nms_thresh,
+                                    int pre_nms_top_n, float* out_boxes, float* out_scores, int* out_classes, int* out_counts, void* stream) {
+  return fcos_decode_impl(cls_logits, ld_cls, ltrb, ld_box, nullptr, ctr_logits, ld_ctr, N, nlev, H, W, strides, num_classes, 2, pre_nms_thresh,
+                          pre_nms_top_n, out_boxes, out_scores, out_classes, out_counts, stream);
+}
+
 /* Generic per-level "threshold + top-k" selection on rows of K class logits (RetinaNet: retina_rotated.py:296-340 / d2
  * inference_single_image; RepPoints: rpd.py:717-765), for the whole batch in one launch.  logits (N, R, ld) with R = sum rows[l]
  * (level-major).  by_row_max = 0: candidates are (row, class) pairs with sigmoid(logit) > thresh, top_n best per (image, level);
@@ -259,7 +278,7 @@ extern "C" int sod_dense_topk_select(const float* logits, int ld, int N, int nle
   if (N <= 0 || nlev <= 0 || nlev > SOD_MAX_LEVELS || num_classes <= 0 || ld < num_classes || top_n <= 0 || top_n >= 65536) return SOD_EARG;
   DecodeArgs a{};
   a.cls = logits; a.N = N; a.nlev = nlev; a.K = num_classes; a.ld_cls = ld; a.ld_box = 0;
-  a.ctr_col_box = a.ctr_col_cls = -1; a.top_n = top_n; a.thresh = score_thresh; a.mode = by_row_max ? 2 : 1;
+  a.top_n = top_n; a.thresh = score_thresh; a.mode = by_row_max ? 2 : 1;
   long long R = 0;
   for (int l = 0; l < nlev; ++l) {
     if (rows[l] <= 0 || (long long)rows[l] * num_classes >= (1ll << 31)) return SOD_EARG;

@@ -314,7 +314,16 @@ __device__ __forceinline__ float centerness_of(float l, float t, float r, float 
   return sqrtf((fminf(l, r) / fmaxf(l, r)) * (fminf(t, b) / fmaxf(t, b)));
 }
 
-template <bool WITH_INDEX>
+// fcos_rpd_s1_topk.py:25-54: centerness (no square root) to the power of the box's slenderness min(w/h, h/w) as seen from the location:
+// the score falls off more slowly along the long side of a slender box.  The libm powf (~1 ulp), not exp2(r * log2(c)) of the hardware.
+__device__ __forceinline__ float slender_centerness_of(float l, float t, float r, float b) {
+  const float c = (fminf(l, r) / fmaxf(l, r)) * (fminf(t, b) / fmaxf(t, b));
+  const float q = (l + r) / (t + b);
+  return powf(c, fminf(q, 1.f / q));
+}
+
+// SLENDER: the centerness target (and with it the key of the top-k pass and the two centerness sums) is slender_centerness_of
+template <bool WITH_INDEX, bool SLENDER = false>
 __global__ __launch_bounds__(256) void fcos_assign_kernel(const AssignArgs a, float* __restrict__ part) {
   __shared__ float red[4];
   const int n = blockIdx.y;
@@ -364,7 +373,10 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(const AssignArgs a, fl
     int owner = -1;
     if (g1 > g0 && best != 100000000.f) {
       label = a.classes[bi];
-      if (label >= 0 && label != a.num_classes) { c = centerness_of(bl, bt, br, bb); npos += 1.f; sctr += c; owner = bi; }
+      if (label >= 0 && label != a.num_classes) {
+        c = SLENDER ? slender_centerness_of(bl, bt, br, bb) : centerness_of(bl, bt, br, bb);
+        npos += 1.f; sctr += c; owner = bi;
+      }
     }
     const long long o = (long long)n * a.L + loc;
     a.labels[o] = label;
@@ -729,11 +741,16 @@ extern "C" int sod_fcos_assign(const float* boxes, const int* classes, const int
   return SOD_OK;
 }
 
-extern "C" int sod_fcos_assign_topk(const float* boxes, const int* classes, const int* box_offsets, int N,
-                                    int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride,
-                                    const float* lvl_lo, const float* lvl_hi, float radius, int num_classes, int topk,
-                                    int* labels, float* reg_targets, float* ctr_targets, int* gt_index, unsigned char* sel,
-                                    float* stats3, float* ws, void* stream) {
+#define SOD_ASSIGN_TOPK_PARAMS                                                                                              \
+  const float *boxes, const int *classes, const int *box_offsets, int N, int nlevels, const int *lvl_h, const int *lvl_w,         \
+      const int *lvl_stride, const float *lvl_lo, const float *lvl_hi, float radius, int num_classes, int topk, int *labels,      \
+      float *reg_targets, float *ctr_targets, int *gt_index, unsigned char *sel, float *stats3, float *ws, void *stream
+#define SOD_ASSIGN_TOPK_ARGS                                                                                                    \
+  boxes, classes, box_offsets, N, nlevels, lvl_h, lvl_w, lvl_stride, lvl_lo, lvl_hi, radius, num_classes, topk, labels, reg_targets, \
+      ctr_targets, gt_index, sel, stats3, ws, stream
+
+template <bool SLENDER>
+static int assign_topk_impl(SOD_ASSIGN_TOPK_PARAMS) {
   if (!stats3 || !ws || !gt_index || !sel || topk < 1 || topk > TOPK_MAX) return SOD_EARG;
   AssignArgs a{};
   int gx = 0;
@@ -742,12 +759,17 @@ extern "C" int sod_fcos_assign_topk(const float* boxes, const int* classes, cons
   if (rc) return rc;
   a.gt_index = gt_index; a.sel = sel; a.topk = topk;
   hipStream_t st = (hipStream_t)stream;
-  SOD_LAUNCH(fcos_assign_kernel<true>, dim3(gx, N), dim3(256), 0, st, a, ws);              // partials: slot 0 num_pos, slot 2 sum ctr
+  SOD_LAUNCH((fcos_assign_kernel<true, SLENDER>), dim3(gx, N), dim3(256), 0, st, a, ws);   // partials: slot 0 num_pos, slot 2 sum ctr
   SOD_LAUNCH(fcos_topk_select_kernel, dim3(TOPK_BLOCKS), dim3(256), 0, st, a, ws);         // slot 1: sum ctr over the selection
   SOD_LAUNCH(finish_sum3_kernel, dim3(1), dim3(256), 0, st, ws, gx * N, TOPK_BLOCKS * 4, gx * N, stats3);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
+
+extern "C" int sod_fcos_assign_topk(SOD_ASSIGN_TOPK_PARAMS) { return assign_topk_impl<false>(SOD_ASSIGN_TOPK_ARGS); }
+
+// FCOSRepPoints (fcos_rpd_s1_topk.py:25-134): the same two passes ranking by, and writing, the slender centerness
+extern "C" int sod_fcos_assign_topk_slender(SOD_ASSIGN_TOPK_PARAMS) { return assign_topk_impl<true>(SOD_ASSIGN_TOPK_ARGS); }
 
 static int fill_regctr(RegCtrArgs& a, int nlevels, const int* lvl_h, const int* lvl_w, const int* lvl_stride) {
   if (nlevels <= 0 || nlevels > SOD_MAX_LEVELS) return SOD_EARG;

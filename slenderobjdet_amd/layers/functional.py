@@ -948,10 +948,12 @@ def fcos_assign(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_intere
     return labels, reg, ctr, stats
 
 
-def fcos_assign_topk(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_interest, radius, num_classes, topk):
+def fcos_assign_topk(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_interest, radius, num_classes, topk, slender=False):
     """``fcos_assign`` plus the ``topk`` most central positive locations of every gt box (fcos_topk.py:24-101), no host sync.
     Returns labels, reg_targets, ctr_targets as ``fcos_assign`` (bit-identical), gt_index (N,L) i32 (index into the concatenated gt
-    list on foreground locations, -1 elsewhere), sel (N,L) u8 and stats3 (3,) = [num_pos, sum_ctr over sel, sum_ctr over foreground]."""
+    list on foreground locations, -1 elsewhere), sel (N,L) u8 and stats3 (3,) = [num_pos, sum_ctr over sel, sum_ctr over foreground].
+    ``slender`` (FCOSRepPoints, fcos_rpd_s1_topk.py:25-54): centerness = (lr ratio * tb ratio) ** min(w/h, h/w) instead of its square
+    root, as ranking score, as ctr_targets and in the two sums; everything else bit-identical."""
     dev = box_offsets.device
     _chk(boxes, torch.float32, "boxes"); _chk(classes, torch.int32, "classes"); _chk(box_offsets, torch.int32, "box_offsets")
     L = sum(h * w for h, w in lvl_hw)
@@ -962,7 +964,7 @@ def fcos_assign_topk(boxes, classes, box_offsets, N, lvl_hw, strides, sizes_of_i
     sel = torch.empty((N, L), dtype=torch.uint8, device=dev)
     stats3 = torch.empty(3, dtype=torch.float32, device=dev)
     nl = len(lvl_hw)
-    call("sod_fcos_assign_topk", ptr(boxes), ptr(classes), ptr(box_offsets), N, nl,
+    call("sod_fcos_assign_topk_slender" if slender else "sod_fcos_assign_topk", ptr(boxes), ptr(classes), ptr(box_offsets), N, nl,
          ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p),
          ctypes.cast(_int_arr(strides), ctypes.c_void_p),
          ctypes.cast(_float_arr([s[0] for s in sizes_of_interest]), ctypes.c_void_p),
@@ -1055,6 +1057,27 @@ def fcos_decode(cls_buf, box_buf, scales, level_hw, strides, num_classes, center
          ctypes.cast(_int_arr([h for h, _ in level_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in level_hw]), ctypes.c_void_p),
          ctypes.cast(_int_arr(strides), ctypes.c_void_p), int(num_classes), 4 if centerness_on_reg else -1, -1 if centerness_on_reg else int(num_classes),
          1 if norm_reg_targets else 0, float(pre_nms_thresh), int(pre_nms_top_n), ptr(boxes), ptr(scores), ptr(classes), ptr(counts), stream_ptr())
+    return boxes, scores, classes, counts
+
+
+def fcos_decode_ltrb(cls_buf, ltrb, ctr, level_hw, strides, num_classes, pre_nms_thresh, pre_nms_top_n):
+    """``fcos_decode`` on regression rows that already are LTRB distances (FCOSRepPoints: no exp, no Scale, no stride).  cls_buf (N, L, ld)
+    logits, ltrb (N, L, >= 4) distances, ctr (N, L, ld_ctr) with the centerness logit in column 0; outputs as ``fcos_decode``."""
+    _chk(cls_buf, torch.float32, "cls_buf"); _chk(ltrb, torch.float32, "ltrb"); _chk(ctr, torch.float32, "ctr")
+    N, L, ld_cls = cls_buf.shape
+    nlev = len(level_hw)
+    if L != sum(h * w for h, w in level_hw) or ltrb.shape[:2] != (N, L) or ctr.shape[:2] != (N, L):
+        raise _C.SlenderHipError("fcos_decode_ltrb: prediction buffers do not match the level geometry")
+    M = nlev * int(pre_nms_top_n)
+    dev = cls_buf.device
+    boxes = torch.empty((N, M, 4), dtype=torch.float32, device=dev)
+    scores = torch.empty((N, M), dtype=torch.float32, device=dev)
+    classes = torch.empty((N, M), dtype=torch.int32, device=dev)
+    counts = torch.empty((N, nlev), dtype=torch.int32, device=dev)
+    call("sod_fcos_decode_ltrb", ptr(cls_buf), ld_cls, ptr(ltrb), ltrb.shape[-1], ptr(ctr), ctr.shape[-1] if ctr.dim() == 3 else 1, N, nlev,
+         ctypes.cast(_int_arr([h for h, _ in level_hw]), ctypes.c_void_p), ctypes.cast(_int_arr([w for _, w in level_hw]), ctypes.c_void_p),
+         ctypes.cast(_int_arr(strides), ctypes.c_void_p), int(num_classes), float(pre_nms_thresh), int(pre_nms_top_n), ptr(boxes), ptr(scores),
+         ptr(classes), ptr(counts), stream_ptr())
     return boxes, scores, classes, counts
 
 
@@ -1518,6 +1541,82 @@ def reppoints_finalize(focal_sum, init_sums, refine_sums, normalizer, momentum, 
     out = torch.empty(3, dtype=torch.float32, device=focal_sum.device)
     call("sod_reppoints_finalize", ptr(focal_sum), ptr(init_sums), ptr(refine_sums), ptr(normalizer), float(momentum), int(num_images),
          float(init_weight), ptr(out), stream_ptr())
+    return out
+
+
+# ----------------------------------------------------------------------------------------------- FCOSRepPoints
+def level_scale_fwd(x, scale):
+    """Scale (layers/scale.py) on fp32 rows: x * scale[0] with the scalar read on the device."""
+    _chk(x, torch.float32, "x"); _chk(scale, torch.float32, "scale")
+    y = torch.empty_like(x)
+    call("sod_level_scale_fwd", ptr(x), ptr(scale), ptr(y), x.numel(), stream_ptr())
+    return y
+
+
+def level_scale_bwd(dy, x, scale, dscale):
+    """-> dx = dy * scale[0]; adds sum(dy * x) (fixed order) to ``dscale`` (one float, e.g. an element of the gradient arena)."""
+    _chk(dy, torch.float32, "dy"); _chk(x, torch.float32, "x"); _chk(scale, torch.float32, "scale"); _chk(dscale, torch.float32, "dscale")
+    dx = torch.empty_like(x)
+    call("sod_level_scale_bwd", ptr(dy), ptr(x), ptr(scale), ptr(dx), x.numel(), ptr(dscale), ptr(reduce_ws(x.device)), stream_ptr())
+    return dx
+
+
+def points2ltrb_fwd(pts, add, loc_stride, point_stride, num_points, ltrb, boxes, out_img_stride, arg, arg_img_stride):
+    """One level: pts (N,H,W,ld) fp32 (+ add) -> LTRB distances / decoded boxes / arg indices, slices of the concatenated (N,L,4) / (N,L)
+    buffers (``boxes`` and ``arg`` optional)."""
+    _chk(pts, torch.float32, "pts"); _chk(add, torch.float32, "add"); _chk(ltrb, torch.float32, "ltrb"); _chk(boxes, torch.float32, "boxes")
+    _chk(arg, torch.int32, "arg")
+    N, H, W, ld = pts.shape
+    call("sod_points2ltrb_fwd", ptr(pts), ptr(add), ld, N, H, W, int(loc_stride), float(point_stride), num_points, ptr(ltrb), ptr(boxes),
+         out_img_stride, ptr(arg), arg_img_stride, stream_ptr())
+
+
+def points2ltrb_bwd(dltrb, out_img_stride, arg, arg_img_stride, shape, point_stride, num_points, want_f32=True, want_bf16=False):
+    N, H, W, ld = shape
+    d32 = torch.empty(shape, dtype=torch.float32, device=dltrb.device) if want_f32 else None
+    d16 = torch.empty(shape, dtype=torch.bfloat16, device=dltrb.device) if want_bf16 else None
+    call("sod_points2ltrb_bwd", ptr(dltrb), out_img_stride, ptr(arg), arg_img_stride, ld, N, H, W, float(point_stride), num_points, ptr(d32), ptr(d16),
+         stream_ptr())
+    return d32, d16
+
+
+def fcos_rpd_refine_targets(gt_boxes, gt_classes, box_offsets, counts, candidates, image_hw, lvl_hw, strides, num_classes, thresholds, labels,
+                            allow_low_quality=True):
+    """pairwise_iou + Matcher of every image's gt boxes against its own candidate boxes (N, L, 4), then the FCOSRepPoints refine labels,
+    for the whole batch without a host read.  ``counts``: the per-image gt counts as the host knows them.  Returns matched_vals (N,L)
+    f32, matches (N,L) i32, match_labels (N,L) i8, cls (N,L) i32 in {-1, 0..K-1, K}, cls_bg (N,L) i32 (-1 -> K) and refine_ltrb (N,L,4)."""
+    _chk(gt_boxes, torch.float32, "gt_boxes"); _chk(gt_classes, torch.int32, "gt_classes"); _chk(box_offsets, torch.int32, "box_offsets")
+    _chk(candidates, torch.float32, "candidates"); _chk(image_hw, torch.float32, "image_hw")
+    N, L = candidates.shape[:2]
+    if L != sum(h * w for h, w in lvl_hw) or len(counts) != N or box_offsets.numel() != N + 1 or image_hw.numel() != 2 * N:
+        raise _C.SlenderHipError("fcos_rpd_refine_targets: inputs do not match the batch / level geometry")
+    total, max_gt = int(sum(counts)), int(max(counts))
+    if max_gt > 4096:
+        raise _C.SlenderHipError("fcos_rpd_refine_targets: more than 4096 gt boxes in one image")
+    if total and (gt_boxes.shape[0] < total or gt_classes.numel() < total):
+        raise _C.SlenderHipError("fcos_rpd_refine_targets: fewer gt boxes than the counts say")
+    dev = candidates.device
+    vals = torch.empty((N, L), dtype=torch.float32, device=dev)
+    matches = torch.empty((N, L), dtype=torch.int32, device=dev)
+    mlab = torch.empty((N, L), dtype=torch.int8, device=dev)
+    cls = torch.empty((N, L), dtype=torch.int32, device=dev)
+    cls_bg = torch.empty((N, L), dtype=torch.int32, device=dev)
+    ltrb = torch.empty((N, L, 4), dtype=torch.float32, device=dev)
+    ws = torch.empty(max(total, 1), dtype=torch.int32, device=dev)
+    call("sod_fcos_rpd_refine_targets", ptr(gt_boxes) if total else None, ptr(gt_classes) if total else None, ptr(box_offsets), N, total, max_gt,
+         ptr(candidates), ptr(image_hw), len(lvl_hw), ctypes.cast(_int_arr([h for h, _ in lvl_hw]), ctypes.c_void_p),
+         ctypes.cast(_int_arr([w for _, w in lvl_hw]), ctypes.c_void_p), ctypes.cast(_int_arr(strides), ctypes.c_void_p), int(num_classes),
+         float(thresholds[0]), float(thresholds[1]), int(labels[0]), int(labels[1]), int(labels[2]), 1 if allow_low_quality else 0,
+         ptr(vals), ptr(matches), ptr(mlab), ptr(cls), ptr(cls_bg), ptr(ltrb), ptr(ws), stream_ptr())
+    return vals, matches, mlab, cls, cls_bg, ltrb
+
+
+def fcos_rpd_finalize(focal_sum, iou_sum, smoothl1_sum, bce_sum, stats3, n_refine, inv_world):
+    """-> out8: [cls_loss, reg_loss_init, reg_loss, centerness_loss, d reg_loss_init / d iou_sum, d reg_loss / d smoothl1_sum,
+    d centerness_loss / d bce_sum, 1]."""
+    out = torch.empty(8, dtype=torch.float32, device=stats3.device)
+    call("sod_fcos_rpd_finalize", ptr(focal_sum), ptr(iou_sum), ptr(smoothl1_sum), ptr(bce_sum), ptr(stats3), ptr(n_refine), float(inv_world),
+         ptr(out), stream_ptr())
     return out
 
 
