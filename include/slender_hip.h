@@ -446,6 +446,25 @@ int sod_batched_nms_run(const long long* order, int B, int M, int box_dim, float
  * |angle| <= 1 degree clipped), boxes with a side <= min_size are emptied (score = -inf). */
 int sod_rpn_clip_filter(float* boxes, float* scores, const float* image_hw, int B, int M, int box_dim, float min_size, int* bad_count,
                         void* stream);
+/* Test-time augmentation, the merge step (detectron2 GeneralizedRCNNWithTTA._inverse_augmented_boxes + the candidate list of
+ * _merge_detections; restated in DESIGN.md section 12): the detections of S augmented runs, concatenated (boxes (T, 4) XYXY in the
+ * augmented image's pixels, scores (T), classes (T); run s owns rows det_off[s] .. det_off[s + 1]), are mapped back to the output size
+ * of their image and packed into the padded candidate layout of sod_batched_nms_*: out_boxes (B, A * D, 4), out_scores (B, A * D),
+ * out_classes (B, A * D).  Run s belongs to image run_image[s] and fills slots run_slot[s] * D .. + D of it; the augmented image was
+ * run_h[s] x run_w[s], mirrored when run_flip[s]; run_sx[s] = W / w_a and run_sy[s] = H / h_a are computed by the caller in double and
+ * rounded once (numpy's float32-array-times-Python-float of ResizeTransform.inverse); out_hw (B, 2) ints = (H, W) per image.
+ * Slot a * D + d is EMPTY (score -inf, zero box, class 0) when d >= the run's count, when a coordinate or the score is not finite,
+ * when score <= score_thresh, or when no run was given for (image, a).  Otherwise: x1' = w_a - x2, x2' = w_a - x1 if flipped; x *= sx,
+ * y *= sy; clip to [0, W] x [0, H].  Boxes of zero area stay candidates.  Slot order = run order, so a stable sort by score gives ties
+ * to the earlier augmentation.  det_off, the run_* tables and out_hw are HOST arrays (they travel as kernel arguments); the rest are
+ * device pointers (boxes / scores / classes may be NULL when T = 0).  One launch, one thread per slot.  SOD_EARG: B * A above
+ * SOD_TTA_MAX_RUNS, a run with more than D detections, offsets that decrease or pass T, an (image, slot) pair given twice or out of
+ * range; SOD_EALIGN: boxes or out_boxes not 16-byte aligned. */
+#define SOD_TTA_MAX_RUNS 64
+int sod_tta_merge_candidates(const float* boxes, const float* scores, const int* classes, int T, const int* det_off, int S,
+                             const int* run_image, const int* run_slot, const int* run_h, const int* run_w, const int* run_flip,
+                             const float* run_sx, const float* run_sy, const int* out_hw, int B, int A, int D, float score_thresh,
+                             float* out_boxes, float* out_scores, int* out_classes, void* stream);
 /* detectron2 nms_rotated / box_iou_rotated (csrc/nms_rotated, csrc/box_iou_rotated; reached through RRPN / RROIHeads selected by
  * configs/rotated/Base-RRCNN-FPN.yaml:10-36 and pairwise_iou at retina_rotated.py:276): boxes (n,5) = (cx,cy,w,h,angle_deg). */
 int sod_nms_rotated(const float* boxes, const long long* order, int n, float iou_threshold, long long* keep, int* num_keep,

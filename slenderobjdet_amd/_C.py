@@ -91,6 +91,7 @@ _SIGS = {
     "sod_batched_nms_prepare": [_P, _P, _P, _I, _I, _I, _P, _P],
     "sod_batched_nms_run": [_P, _I, _I, _I, _F, _I, _P, _P, _P, _P],
     "sod_rpn_clip_filter": [_P, _P, _P, _I, _I, _I, _F, _P, _P],
+    "sod_tta_merge_candidates": [_P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _F, _P, _P, _P, _P],
     "sod_nms": [_P, _P, _I, _F, _P, _P, _P, _P],
     "sod_nms_rotated": [_P, _P, _I, _F, _P, _P, _P, _P],
     "sod_box_iou_rotated": [_P, _I, _P, _I, _P, _P],

@@ -5,14 +5,16 @@
                '--num-gpus', '8']; runpy.run_path('train_net.py', run_name='__main__')"
 
 The training hot path and the slender-object COCO box evaluation (slenderobjdet_amd.evaluation) are backed by real code;
-TTA, the rotated evaluator and dataset names resolve to objects that raise ``NotImplementedError`` when used (out of scope,
-SURVEY.md §2.1).
+after the import alone TTA, the rotated evaluator and dataset names resolve to objects that raise ``NotImplementedError`` when used
+(SURVEY.md §2.1).
 
-The rotated evaluator exists (slenderobjdet_amd.evaluation.RotatedCOCOEvaluator) but is bound on request only, so that importing
-this module keeps what it has always bound:
+The rotated evaluator (slenderobjdet_amd.evaluation.RotatedCOCOEvaluator) and test-time augmentation
+(slenderobjdet_amd.modeling.GeneralizedRCNNWithTTA, what ``Trainer.test_with_TTA`` wraps the model in, train_net.py:128-141) exist
+but are bound on request only, so that importing this module keeps what it has always bound:
 
     import slenderobjdet_amd.dropin as dropin
     dropin.bind_rotated_evaluator()      # detectron2.evaluation.RotatedCOCOEvaluator is now the real class
+    dropin.bind_tta()                    # detectron2.modeling.GeneralizedRCNNWithTTA / DatasetMapperTTA are now the real classes
 """
 import sys
 import types
@@ -114,6 +116,15 @@ def bind_rotated_evaluator():
     """Rebinds ``detectron2.evaluation.RotatedCOCOEvaluator`` (a stub after ``install()``) to the on-device evaluator; returns it."""
     _mod("detectron2.evaluation", RotatedCOCOEvaluator=_evaluation.RotatedCOCOEvaluator)
     return _evaluation.RotatedCOCOEvaluator
+
+
+def bind_tta():
+    """Rebinds ``detectron2.modeling.GeneralizedRCNNWithTTA`` (a stub after ``install()``) to the on-device wrapper and exports
+    ``DatasetMapperTTA`` next to it; returns the wrapper class."""
+    from .modeling import test_time_augmentation as _tta
+
+    _mod("detectron2.modeling", GeneralizedRCNNWithTTA=_tta.GeneralizedRCNNWithTTA, DatasetMapperTTA=_tta.DatasetMapperTTA)
+    return _tta.GeneralizedRCNNWithTTA
 
 
 install()

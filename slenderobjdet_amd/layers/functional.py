@@ -1128,6 +1128,41 @@ def rpn_clip_filter(boxes, scores, image_hw, min_size):
     return bad
 
 
+TTA_MAX_RUNS = 64      # SOD_TTA_MAX_RUNS: (image, augmentation) pairs of one merge launch
+
+
+def tta_merge_candidates(boxes, scores, classes, det_off, runs, out_sizes, A, D, score_thresh):
+    """The merge step of test-time augmentation in one launch (no host read): the detections of S augmented runs - boxes (T, 4) XYXY in
+    the augmented images' pixels, scores (T), classes (T) int32, concatenated, run s owning rows det_off[s] .. det_off[s + 1] - are
+    un-flipped, scaled to and clipped at the output size of their image and packed into the padded candidate layout ``batched_nms_topk``
+    consumes.  ``runs``: per run (image index b, slot a of the run inside its image, h_a, w_a, flip); ``out_sizes``: (H, W) per image;
+    ``A`` slots of ``D`` detections per image.  Returns boxes (B, A * D, 4), scores (B, A * D) (-inf = empty slot), classes (B, A * D).
+    A slot is empty beyond its run's count, for a non-finite row and for score <= ``score_thresh``.  det_off / runs / out_sizes are
+    host sequences; the scale factors W / w_a and H / h_a are computed here in double and rounded once."""
+    _chk(boxes, torch.float32, "boxes"); _chk(scores, torch.float32, "scores"); _chk(classes, torch.int32, "classes")
+    T, S, B = int(scores.shape[0]), len(runs), len(out_sizes)
+    if boxes.shape != (T, 4) or classes.shape != (T,) or len(det_off) != S + 1:
+        raise _C.SlenderHipError("tta_merge_candidates: boxes (T, 4), scores (T), classes (T) and S + 1 offsets expected")
+    if any(int(r[2]) <= 0 or int(r[3]) <= 0 for r in runs):
+        raise _C.SlenderHipError("tta_merge_candidates: augmented sizes must be positive")
+    if any(not 0 <= int(r[0]) < B for r in runs):
+        raise _C.SlenderHipError("tta_merge_candidates: run of an image that is not in out_sizes")
+    A, D = int(A), int(D)
+    dev = boxes.device
+    out_b = torch.empty((B, A * D, 4), dtype=torch.float32, device=dev)
+    out_s = torch.empty((B, A * D), dtype=torch.float32, device=dev)
+    out_c = torch.empty((B, A * D), dtype=torch.int32, device=dev)
+    col = lambda k: ctypes.cast(_int_arr([r[k] for r in runs]), ctypes.c_void_p)
+    sx = _float_arr([float(out_sizes[int(r[0])][1]) / int(r[3]) for r in runs])
+    sy = _float_arr([float(out_sizes[int(r[0])][0]) / int(r[2]) for r in runs])
+    hw = _int_arr([v for s in out_sizes for v in s[:2]])
+    call("sod_tta_merge_candidates", ptr(boxes) if T else None, ptr(scores) if T else None, ptr(classes) if T else None, T,
+         ctypes.cast(_int_arr(det_off), ctypes.c_void_p), S, col(0), col(1), col(2), col(3), col(4), ctypes.cast(sx, ctypes.c_void_p),
+         ctypes.cast(sy, ctypes.c_void_p), ctypes.cast(hw, ctypes.c_void_p), B, A, D, float(score_thresh), ptr(out_b), ptr(out_s), ptr(out_c),
+         stream_ptr())
+    return out_b, out_s, out_c
+
+
 def nms_rotated(boxes, scores, iou_threshold):
     """detectron2.layers.nms_rotated: boxes (n,5) = (cx,cy,w,h,angle_deg)."""
     return _nms_single("sod_nms_rotated", boxes, scores, iou_threshold)

@@ -2,3 +2,4 @@
 from .backbone import BACKBONE_REGISTRY, Backbone, build_backbone
 from .meta_arch import META_ARCH_REGISTRY, build_model
 from .shape_spec import ShapeSpec
+from .test_time_augmentation import DatasetMapperTTA, GeneralizedRCNNWithTTA, tta_plan

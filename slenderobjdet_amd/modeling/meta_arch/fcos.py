@@ -27,7 +27,7 @@ from torch.autograd.function import once_differentiable
 from ...layers import functional as HF
 from ...layers.deform_conv import DFConv2d
 from ...layers.nn import ConvGnRelu, HipConv2d, HipGroupNorm, _arena_of, group_norm_relu
-from ...structures import Boxes, ImageList, Instances
+from ...structures import Boxes, ImageList, Instances, PreparedInputs
 from ...utils import comm
 from ..backbone import build_backbone
 from ..postprocessing import batched_nms_instances, detector_postprocess
@@ -466,7 +466,13 @@ class FCOSV2(nn.Module):
     def preprocess_image(self, batched_inputs):
         """fcosv2.py:268-275: normalise, pad to size_divisibility, batch — one kernel per image straight into the
         NHWC(8) bf16 batch buffer (the H2D copy of the uint8 image is the only other traffic).  In training mode a batch that
-        ``prefetch`` has already been given comes back as an ImageList around its FrozenPrefix (which ``backbone`` resumes from)."""
+        ``prefetch`` has already been given comes back as an ImageList around its FrozenPrefix (which ``backbone`` resumes from).
+        A ``structures.PreparedInputs`` already carries its batch: that ImageList is returned as it is."""
+        if isinstance(batched_inputs, PreparedInputs):
+            t = batched_inputs.images.tensor
+            if not (torch.is_tensor(t) and t.dim() == 4 and t.shape[-1] == 8 and t.dtype == HF.ACT_DTYPE and t.device.type == self.device.type):
+                raise ValueError(f"PreparedInputs.images must be an NHWC(8) {HF.ACT_DTYPE} batch on {self.device}")
+            return batched_inputs.images
         if self.training and getattr(self, "_prefetched", None) is not None:
             images = self._take_prefetched(batched_inputs)
             if images is not None:

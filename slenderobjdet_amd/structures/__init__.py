@@ -216,6 +216,21 @@ class ImageList:
         return ImageList(batch.contiguous(), sizes)
 
 
+class PreparedInputs(list):
+    """``batched_inputs`` whose images are already on the device as the batch the backbone reads: a list of the per-image dicts (they
+    need no "image"; "height" / "width" are honoured by the models' postprocess as usual) that carries ``images``, an ImageList over an
+    NHWC(8) batch (n, Hp, Wp, 8) of ``layers.functional.ACT_DTYPE`` - normalised, zero-padded to the backbone's size divisibility,
+    channels 3..7 zero - with the unpadded (h, w) of every image in ``image_sizes``.  ``preprocess_image`` of every meta-architecture
+    returns ``images`` as it is; ``data.transforms.DeviceInputPipeline`` produces such batches (test-time augmentation feeds its
+    resized / flipped copies of one image this way).  Inference only: it bypasses the training prefetch."""
+
+    def __init__(self, dicts, images):
+        super().__init__(dicts)
+        if len(images) != len(self):
+            raise ValueError(f"PreparedInputs: {len(self)} dicts for {len(images)} images")
+        self.images = images
+
+
 class RotatedBoxes(Boxes):
     """detectron2.structures.RotatedBoxes (source absent): (N,5) = (cx, cy, w, h, angle in degrees, CCW positive)."""
 
