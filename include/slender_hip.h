@@ -886,6 +886,36 @@ int sod_coco_match_rotated(const int* gt_off, const float* gt_box5, const unsign
                            const double* iou_thr, int T, const double* ranges, int A, const long long* scratch_off, float* scratch,
                            unsigned long long* dt_matched, unsigned long long* dt_ignored, int* npig, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * RotatedRetinaNet (slenderobjdet_amd/modeling/meta_arch/rotated_retinanet.py; csrc/rotated_retina.hip): detectron2's rotated pieces in
+ * RetinaNet's slots, the intent of the reference's retina_rotated.py (:71, :271).
+ *
+ * sod_retina_label_rotated: label_anchors of the WHOLE batch in two launches.  anchors (R, 5); gt_boxes (N, Gmax, 5) / gt_classes
+ *   (N, Gmax) padded, gt_counts (N) int32 ON THE DEVICE (clamped to [0, Gmax]; never read back); Matcher([lo, hi], three labels in
+ *   {-1, 0, 1}, allow_low_quality) over pairwise_iou_rotated(gt, anchors) per image; gt_labels (N, R): matcher label 0 -> num_classes,
+ *   -1 -> -1, 1 -> class of the matched gt; gt_deltas (N, R, 5) = Box2BoxTransformRotated.get_deltas(anchor, matched gt) (weights5 host);
+ *   an image without gts: all num_classes / all 0.  gt_best_ws: N * Gmax unsigned words, zeroed by the call.  Labels and matches are
+ *   identical to sod_anchor_match_rotated + sod_retina_targets' mapping per image.  Gmax <= SOD_RETINA_LABEL_MAX_GT (LDS), N <= 65535.
+ * sod_retina_box5_loss_*: sod_retina_box_loss_* for 5 deltas per anchor (anchor a of pixel p at p*pitch + a*5, pitch >= A*5).
+ * sod_retina_decode_rotated: Box2BoxTransformRotated.apply_deltas for the candidates of sod_dense_topk_select in one launch: slot (n, m)
+ *   of level m / top_n holds level-local row rows[n, m]; anchor = row + level_row0[level] (host array, nlev <= 8, M = nlev * top_n);
+ *   out (N, M, 5); a slot whose score is -inf or whose box is not finite gets five zeros; the rest is bit-equal to
+ *   sod_box2box_apply_deltas (box_dim 5) on the gathered rows. */
+#define SOD_RETINA_LABEL_MAX_GT 1024
+int sod_retina_label_rotated(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts, int N,
+                             int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
+                             int allow_low_quality, int num_classes, const float* weights5, int* gt_labels, float* gt_deltas,
+                             unsigned* gt_best_ws, void* stream);
+int sod_retina_box5_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
+                             int num_classes, float beta, float* sums2, float* normalizer, float momentum, float* ws, void* stream);
+int sod_retina_box5_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
+                             int num_classes, float beta, const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream);
+int sod_retina_box5_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
+                                 int num_classes, float beta, const float* grad_num, const float* grad_den, float* dpred, void* stream);
+int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors, const int* rows, const float* scores, int N, int P,
+                              int A, int M, int top_n, const int* level_row0, int nlev, const float* weights5, float scale_clamp,
+                              float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1385,6 +1385,62 @@ def retina_box_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes,
          ptr(grad_den), ptr(dpred), stream_ptr())
 
 
+# ----------------------------------------------------------------------------------------------- RotatedRetinaNet
+def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, labels, allow_low_quality, num_classes, weights, ws=None):
+    """label_anchors of the whole batch in two launches: anchors (R, 5), gt_boxes (N, Gmax, 5) / gt_classes (N, Gmax) int32 padded,
+    gt_counts (N) int32 on the device (never read back) -> gt_labels (N, R) int32 in {-1, 0..K-1, K}, gt_deltas (N, R, 5).  ``ws``: N * Gmax
+    int32 words (zeroed by the call); allocated when None."""
+    _chk(anchors, torch.float32, "anchors"); _chk(gt_boxes, torch.float32, "gt_boxes"); _chk(gt_classes, torch.int32, "gt_classes")
+    _chk(gt_counts, torch.int32, "gt_counts")
+    R = anchors.shape[0]
+    N, Gmax = gt_classes.shape
+    if anchors.shape[-1] != 5 or tuple(gt_boxes.shape) != (N, Gmax, 5) or gt_counts.numel() != N or len(weights) != 5:
+        raise _C.SlenderHipError("retina_label_rotated: anchors (R, 5), gt_boxes (N, Gmax, 5), gt_classes (N, Gmax), gt_counts (N), five weights")
+    dev = anchors.device
+    if ws is None:
+        ws = torch.empty(max(N * Gmax, 1), dtype=torch.int32, device=dev)
+    _chk(ws, torch.int32, "ws")
+    if ws.numel() < N * Gmax:
+        raise _C.SlenderHipError("retina_label_rotated: the workspace holds fewer than N * Gmax words")
+    gt_labels = torch.empty((N, R), dtype=torch.int32, device=dev)
+    gt_deltas = torch.empty((N, R, 5), dtype=torch.float32, device=dev)
+    w = _float_arr(weights)
+    call("sod_retina_label_rotated", ptr(anchors), R, ptr(gt_boxes) if Gmax else None, ptr(gt_classes) if Gmax else None, ptr(gt_counts), N, Gmax,
+         float(thresholds[0]), float(thresholds[1]), int(labels[0]), int(labels[1]), int(labels[2]), 1 if allow_low_quality else 0, int(num_classes),
+         ctypes.cast(w, ctypes.c_void_p), ptr(gt_labels), ptr(gt_deltas), ptr(ws), stream_ptr())
+    return gt_labels, gt_deltas
+
+
+def retina_box5_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, normalizer, momentum):
+    sums = torch.empty(2, dtype=torch.float32, device=pred.device)
+    call("sod_retina_box5_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta), ptr(sums),
+         ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
+    return sums
+
+
+def retina_box5_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, grad_num, grad_den, dpred):
+    call("sod_retina_box5_loss_bwd_f32" if is_f32() else "sod_retina_box5_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta),
+         ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
+
+
+def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):
+    """Box2BoxTransformRotated.apply_deltas for the candidates of ``dense_topk_select`` in one launch: pred (N, P, pitch) fp32 deltas
+    (anchor a of pixel p at p*pitch + a*5), anchors (P*A, 5), rows / scores (N, M) -> boxes (N, M, 5); empty (-inf) and non-finite
+    slots are five zeros."""
+    _chk(pred, torch.float32, "pred"); _chk(anchors, torch.float32, "anchors"); _chk(rows, torch.int32, "rows"); _chk(scores, torch.float32, "scores")
+    N, P, pitch = pred.shape
+    M = rows.shape[1]
+    nlev = len(rows_per_level)
+    if anchors.shape != (P * A, 5) or sum(rows_per_level) != P * A or tuple(scores.shape) != (N, M) or rows.shape[0] != N or M != nlev * int(top_n):
+        raise _C.SlenderHipError("retina_decode_rotated: candidates do not match the level geometry")
+    row0 = [sum(rows_per_level[:l]) for l in range(nlev)]
+    out = torch.empty((N, M, 5), dtype=torch.float32, device=pred.device)
+    w = _float_arr(weights)
+    call("sod_retina_decode_rotated", ptr(pred), pitch, ptr(anchors), ptr(rows), ptr(scores), N, P, int(A), M, int(top_n),
+         ctypes.cast(_int_arr(row0), ctypes.c_void_p), nlev, ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(out), stream_ptr())
+    return out
+
+
 # ----------------------------------------------------------------------------------------------- FPN with a norm
 def add_up2(a, b):
     """a + nearest-2x-upsample(b) (d2 FPN top-down sum when a norm follows the lateral conv)."""

@@ -37,8 +37,9 @@ PRED_DGRAD_PAD = True
 FOCAL_FUSED = os.environ.get("SOD_FOCAL_FUSED", "1") != "0"
 
 class RetinaNetHead(nn.Module):
-    def __init__(self, cfg, in_channels, num_anchors):
+    def __init__(self, cfg, in_channels, num_anchors, box_dim=4):
         super().__init__()
+        self.box_dim = box_dim                              # 4: XYXY deltas; 5: (cx, cy, w, h, angle) deltas (RotatedRetinaNet)
         self.num_classes = cfg.MODEL.RETINANET.NUM_CLASSES
         self.num_anchors = num_anchors
         n = cfg.MODEL.RETINANET.NUM_CONVS
@@ -46,18 +47,18 @@ class RetinaNetHead(nn.Module):
         self.bbox_subnet = nn.ModuleList([ConvReluML(in_channels) for _ in range(n)])
         self.kc = num_anchors * self.num_classes            # 720, a multiple of 8
         assert self.kc % 8 == 0
-        self.box_pitch = _ceil8(num_anchors * 4)            # 36 -> 40
+        self.box_pitch = _ceil8(num_anchors * box_dim)      # 36 -> 40
         self.cls_score = HipConv2d(in_channels, self.kc, 3, 1, 1, bias=True)
         self.bbox_pred = HipConv2d(in_channels, self.box_pitch, 3, 1, 1, bias=True)
         # rows a reference checkpoint holds (checkpoint.py drops / restores the pad): A*K scores, A*4 deltas (retina_rotated.py:432-437)
-        self.cls_score.ckpt_rows, self.bbox_pred.ckpt_rows = num_anchors * self.num_classes, num_anchors * 4
+        self.cls_score.ckpt_rows, self.bbox_pred.ckpt_rows = num_anchors * self.num_classes, num_anchors * box_dim
         for u in list(self.cls_subnet) + list(self.bbox_subnet):
             u.conv.init_normal(0.01, 0.0)
         prior = cfg.MODEL.RETINANET.PRIOR_PROB
         with torch.no_grad():
             self.cls_score.init_normal(0.01, -math.log((1 - prior) / prior))
             self.bbox_pred.init_normal(0.01, 0.0)
-            self.bbox_pred.weight[num_anchors * 4:].zero_()
+            self.bbox_pred.weight[num_anchors * box_dim:].zero_()
 
     def run_towers(self, feats):
         c, b = list(feats), list(feats)
@@ -103,7 +104,8 @@ class _RetinaLossFn(torch.autograd.Function):
             sums = HF.retina_giou_loss_fwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
                                            model.scale_clamp, model.loss_normalizer, model.loss_normalizer_momentum)
         else:
-            sums = HF.retina_box_loss_fwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta,
+            box_loss_fwd = HF.retina_box5_loss_fwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_fwd
+            sums = box_loss_fwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta,
                                           model.loss_normalizer, model.loss_normalizer_momentum)    # also advances the EMA normaliser
         dcls_u = None
         # the one-pass kernel is vectorised only (sod_sigmoid_focal_loss_fwd_grad: 4 classes per lane, 32-bit element offsets): other
@@ -149,7 +151,8 @@ class _RetinaLossFn(torch.autograd.Function):
             HF.retina_giou_loss_bwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
                                     model.scale_clamp, g2[1:2], norm, dbox)
         else:
-            HF.retina_box_loss_bwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta, g2[1:2], norm, dbox)
+            box_loss_bwd = HF.retina_box5_loss_bwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_bwd
+            box_loss_bwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta, g2[1:2], norm, dbox)
         grads = []
         for pred, dbuf, kk, tower, scale in ((head.cls_score, dcls, head.kc, cls_t, cls_scale), (head.bbox_pred, dbox, head.box_pitch, box_t, None)):
             dys = [dbuf.view(-1)[o * kk:] for o in offs]
@@ -175,8 +178,10 @@ class _RetinaLossFn(torch.autograd.Function):
         return (None, None, None, None, *grads[0], *grads[1])
 
 
-@META_ARCH_REGISTRY.register()
-class RetinaNet(nn.Module):
+class RetinaNetBase(nn.Module):
+    """Everything RetinaNet is, under a name of its own: RotatedRetinaNet shares it without being a RetinaNet (code that accepts a
+    RetinaNet by isinstance - test-time augmentation merges XYXY boxes - must not take five-column boxes for it)."""
+
     def __init__(self, cfg):
         super().__init__()
         r = cfg.MODEL.RETINANET
@@ -197,8 +202,7 @@ class RetinaNet(nn.Module):
         self.strides = [shapes[f].stride for f in self.in_features]
         ag = cfg.MODEL.ANCHOR_GENERATOR
         self.anchor_sizes, self.anchor_ratios, self.anchor_offset = [list(s) for s in ag.SIZES], [list(a) for a in ag.ASPECT_RATIOS], ag.OFFSET
-        num_anchors = len(self.anchor_sizes[0]) * len(self.anchor_ratios[0])
-        self.head = RetinaNetHead(cfg, shapes[self.in_features[0]].channels, num_anchors)
+        self.head = RetinaNetHead(cfg, shapes[self.in_features[0]].channels, self.num_cell_anchors(cfg), box_dim=self.box_dim)
         self.register_buffer("pixel_mean", torch.Tensor(cfg.MODEL.PIXEL_MEAN).view(-1, 1, 1))
         self.register_buffer("pixel_std", torch.Tensor(cfg.MODEL.PIXEL_STD).view(-1, 1, 1))
         self._mean = [float(v) for v in cfg.MODEL.PIXEL_MEAN]
@@ -206,6 +210,13 @@ class RetinaNet(nn.Module):
         self.register_buffer("loss_normalizer", torch.tensor([100.0]))     # retina_rotated.py:87-88
         self.loss_normalizer_momentum = 0.9
         self._anchor_cache = {}
+
+    box_dim = 4
+
+    @staticmethod
+    def num_cell_anchors(cfg):
+        ag = cfg.MODEL.ANCHOR_GENERATOR
+        return len(ag.SIZES[0]) * len(ag.ASPECT_RATIOS[0])
 
     @property
     def device(self):
@@ -278,3 +289,8 @@ class RetinaNet(nn.Module):
         return batched_nms_instances(boxes, scores, classes, self.nms_threshold, self.max_detections_per_image, image_sizes)
 
     postprocess = FCOSV2.postprocess
+
+
+@META_ARCH_REGISTRY.register()
+class RetinaNet(RetinaNetBase):
+    pass
