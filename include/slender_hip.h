@@ -916,6 +916,26 @@ int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors
                               int A, int M, int top_n, const int* level_row0, int nlev, const float* weights5, float scale_clamp,
                               float* out, void* stream);
 
+/* ---------------------------------------------------------------------------------------------------------
+ * Minimum-area rectangles of polygon annotations (csrc/polygon_geom.hip; host side slenderobjdet_amd/structures/polygons.py): the
+ * rectangle behind the reference's oriented ratio (COCO.compute_ratio) and its rotated ground truth (COCO.compute_rbox,
+ * tools/mask_to_rbox.py), which the reference takes from OpenCV.  All arithmetic is float64.
+ *
+ * xy [P, 2]: the points of all annotations in image coordinates (16-byte aligned, else SOD_EALIGN); ann_off [A + 1]: point offsets,
+ * ann_off[0] = 0, ann_off[A] = P.  rect [A, 5] = (cx, cy, w, h, angle_deg), info [A] = number of hull vertices.
+ * Per annotation: the convex hull of the distinct points, counter-clockwise from the lexicographically smallest (x, y) point, without
+ * collinear vertices; for every hull edge with unit direction u and normal v = (-uy, ux) the extents w along u and h along v of the
+ * points; the edge of least w * h, the FIRST one in hull order among equal areas; centre u * mid_u + v * mid_v; angle
+ * degrees(atan2(-uy, ux)) (detectron2's convention: the width axis is (cos a, -sin a)) folded into (-45, 45] by multiples of 90, w and
+ * h swapped for an odd multiple.  Fewer than 3 hull vertices (one point, coincident or collinear points): rect = the axis-aligned extent
+ * (centre, width, height, 0) and info < 3.  An annotation without points gets zeros and info 0; one with more than
+ * SOD_POLYGON_MAX_POINTS points is not computed (NaN, info -1): the offsets live on the device, so the host side checks them before
+ * the call.  One launch, no workspace, no atomics; A == 0 launches nothing.  SOD_EARG: A < 0 or A > SOD_POLYGON_MAX_ANNS. */
+#define SOD_POLYGON_LDS_POINTS 512           /* annotations up to this many points are staged in LDS, larger ones read global memory */
+#define SOD_POLYGON_MAX_POINTS (1 << 20)
+#define SOD_POLYGON_MAX_ANNS (1 << 24)
+int sod_polygon_min_area_rect(const double* xy, const int* ann_off, int A, double* rect, int* info, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -33,7 +33,9 @@ class COCOEvaluator(DatasetEvaluator):
     def __init__(self, dataset_name, cfg=None, distributed=True, output_dir=None):
         """dataset_name's metadata must carry ``json_file`` (a COCO-format json); ``thing_dataset_id_to_contiguous_id`` and
         ``thing_classes`` are used when present (else the identity map over the sorted category ids).  Only bbox is evaluated:
-        a config that asks for segm or keypoints raises NotImplementedError."""
+        a config that asks for segm or keypoints raises NotImplementedError.  A ``ratio_device`` entry of the metadata ("cuda", "cpu")
+        is handed to CocoGt: the gt ratios then come from structures.polygons.oriented_ratios, one kernel launch on a GPU, instead
+        of the host loop (the constructor keeps the reference's four parameters, so the option travels beside json_file)."""
         self._tasks = _tasks_from_config(cfg)
         extra = [t for t in self._tasks if t != "bbox"]
         if extra:
@@ -45,7 +47,7 @@ class COCOEvaluator(DatasetEvaluator):
         if "json_file" not in self._metadata:
             raise ValueError(f"MetadataCatalog entry '{dataset_name}' has no json_file (a COCO-format annotation file)")
         self._gt = CocoGt(self._metadata["json_file"], id_map=self._metadata.get("thing_dataset_id_to_contiguous_id"),
-                          class_names=self._metadata.get("thing_classes"))
+                          class_names=self._metadata.get("thing_classes"), ratio_device=self._metadata.get("ratio_device"))
         self._do_evaluation = self._gt.has_annotations
         self._gt_dev = None
         self.stats = None

@@ -88,7 +88,9 @@ def gt_ratio(ann):
 class CocoGt:
     """Index of a COCO-format dataset: sorted image and category ids, every annotation with its ratio, and the category maps."""
 
-    def __init__(self, dataset, id_map=None, class_names=None):
+    def __init__(self, dataset, id_map=None, class_names=None, ratio_device=None):
+        """ratio_device: None computes every ratio with the host loop above; a device ("cuda", "cpu") takes the ratios of all annotations
+        from structures.polygons.oriented_ratios - one kernel launch on a GPU - by the same rules."""
         self.dataset = load_json(dataset)
         self.img_ids = sorted({im["id"] for im in self.dataset.get("images", [])})
         cats = self.dataset.get("categories", [])
@@ -99,7 +101,12 @@ class CocoGt:
         self.class_names = list(class_names) if class_names is not None else None
         self.has_annotations = "annotations" in self.dataset
         self.anns = list(self.dataset.get("annotations", []))
-        self.ratios = np.array([float(gt_ratio(a)) for a in self.anns], np.float64)
+        if ratio_device is None:
+            self.ratios = np.array([float(gt_ratio(a)) for a in self.anns], np.float64)
+        else:
+            from ..structures.polygons import oriented_ratios
+
+            self.ratios = oriented_ratios(self.anns, ratio_device)
         self._arrays = None
         self._rotated_arrays = None
 

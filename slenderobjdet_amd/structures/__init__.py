@@ -303,3 +303,6 @@ def pairwise_iou_rotated(boxes1: RotatedBoxes, boxes2: RotatedBoxes):
     from ..layers import functional as HF
 
     return HF.box_iou_rotated(boxes1.tensor.float().contiguous(), boxes2.tensor.float().contiguous())
+
+
+from .polygons import min_area_rects, oriented_ratios, pack_polygons, usable_polygons  # noqa: E402

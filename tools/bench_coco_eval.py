@@ -79,7 +79,11 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--rotated", action="store_true", help="time the rotated-box evaluation (RotatedCOCOEvaluator)")
+    ap.add_argument("--ratio-device", default=None,
+                    help="take the gt ratios from structures.polygons.oriented_ratios on this device, through the metadata's ratio_device (COCOEvaluator only; default: the host loop)")
     a = ap.parse_args()
+    if a.rotated and a.ratio_device is not None:
+        ap.error("--ratio-device applies to COCOEvaluator, not to --rotated")
     dev = torch.device("cuda:0")
     t0 = time.perf_counter()
     synth = synthetic_rotated_coco if a.rotated else synthetic_coco
@@ -91,6 +95,8 @@ def main():
             json.dump(ds, f)
         MetadataCatalog.get("bench_coco_eval").json_file = jf
         t0 = time.perf_counter()
+        if a.ratio_device is not None:
+            MetadataCatalog.get("bench_coco_eval").ratio_device = a.ratio_device
         ev = (RotatedCOCOEvaluator if a.rotated else COCOEvaluator)("bench_coco_eval", None, False)
         t_gt = time.perf_counter() - t0
     flat = predictions_from_numpy(preds, dev)
