@@ -917,6 +917,41 @@ int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors
                               float* out, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
+ * Rotated IoU box loss (csrc/rotated_iou_loss.hip; layers.rotated_iou_loss, RotatedRetinaNet's BBOX_REG_LOSS_TYPE "rotated_iou"):
+ * loss = 1 - IoU(pred, target) on (cx, cy, w, h, angle_deg) boxes.  The IoU is the one of sod_box_iou_rotated, to the bit.
+ *
+ * sod_rotated_iou_loss: the pair operator, the rotated sibling of sod_giou_loss_xyxy.  elem_out[i] = 1 - IoU(boxes1[i], boxes2[i])
+ *   (optional), sum_out[0] = their sum (optional; needs ws), dboxes1 (P, 5) = grad_scale[0] * d loss / d boxes1 (optional; grad_scale
+ *   NULL = 1); the angle's gradient is per degree.  A row whose forward IoU is exactly 0 (disjoint boxes, an area below 1e-14, the
+ *   early-outs of the IoU) gets five zeros: the loss has NO gradient for boxes that do not overlap.  The gradient is the boundary
+ *   integral of the moving rectangle's edges inside the fixed one (no derivative of the clipping's sort and scan); it is exact away
+ *   from the kinks of the IoU (a vertex of one rectangle on an edge of the other; identical rectangles).
+ * sod_retina_riou_loss_{fwd,bwd,bwd_f32}: the contract of sod_retina_giou_loss_* for five deltas per anchor (anchor a of pixel p at
+ *   p*pitch + a*5, pitch >= A*5): positives (0 <= label != num_classes) decode their deltas against the anchor (R, 5) with the
+ *   arithmetic of sod_box2box_apply_deltas (box_dim 5; dw, dh clamped at scale_clamp, angle wrapped into [-180, 180)) and take the pair
+ *   loss against matched_boxes (N, R, 5).  fwd: sums2 = [sum, number of positives], normalizer <- m*normalizer + (1-m)*max(npos, 1).
+ *   bwd: dpred = grad_num[0] / grad_den[0] * d sum / d pred through the decode (d cx / d dx = aw / wx, d w / d dw = w / ww and 0 where
+ *   the clamp is active, d angle_deg / d da = 180 / (pi * wa)); the five columns of every non-positive anchor and the pad columns
+ *   [A*5, pitch) are written as exact zeros.
+ * sod_retina_label_rotated_boxes: sod_retina_label_rotated (same kernels, one template switch, identical labels) writing
+ *   matched_boxes (N, R, 5) = gt_boxes[n, match] for EVERY anchor instead of the deltas; zeros for an image without gts. */
+int sod_rotated_iou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
+                         const float* grad_scale, float* dboxes1, float* ws, void* stream);
+int sod_retina_riou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                             int N, int R, int A, int num_classes, const float* weights5, float scale_clamp, float* sums2,
+                             float* normalizer, float momentum, float* ws, void* stream);
+int sod_retina_riou_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                             int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                             const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream);
+int sod_retina_riou_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                 int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                 const float* grad_num, const float* grad_den, float* dpred, void* stream);
+int sod_retina_label_rotated_boxes(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts,
+                                   int N, int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
+                                   int allow_low_quality, int num_classes, const float* weights5, int* gt_labels,
+                                   float* matched_boxes, unsigned* gt_best_ws, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------
  * Minimum-area rectangles of polygon annotations (csrc/polygon_geom.hip; host side slenderobjdet_amd/structures/polygons.py): the
  * rectangle behind the reference's oriented ratio (COCO.compute_ratio) and its rotated ground truth (COCO.compute_rbox,
  * tools/mask_to_rbox.py), which the reference takes from OpenCV.  All arithmetic is float64.

@@ -4,6 +4,7 @@
 //   * sod_retina_label_rotated: pairwise_iou_rotated + Matcher + class mapping + Box2BoxTransformRotated.get_deltas of the WHOLE batch in
 //     two launches (image = grid.y, the image's gt count read on the device).  Decision-identical to sod_anchor_match_rotated ->
 //     sod_retina_targets' mapping -> sod_box2box_get_deltas per image: the same iou_rotated_lds, the same 64-bit "first maximum wins".
+//     sod_retina_label_rotated_boxes: the same kernels writing the matched gt box itself instead of the deltas (the rotated IoU loss).
 //   * sod_retina_box5_loss_*: retina_box_kernel of detection_ops.hip for 5 deltas per anchor (anchor a of pixel p at p*pitch + a*5).
 //   * sod_retina_decode_rotated: Box2BoxTransformRotated.apply_deltas on the candidates of sod_dense_topk_select, one launch per batch.
 // Latency / HBM-bound fp32 work, no MFMA; the clipping's candidate points live in LDS (rotated_iou.h).
@@ -39,7 +40,7 @@ struct LabelArgs {
   int l0, l1, l2, low_quality, num_classes;
   RW5 w;
   int* labels;               // (N, R)
-  float* deltas;             // (N, R, 5)
+  float* deltas;             // (N, R, 5): the deltas, or the matched gt boxes (retina_label1_rot_kernel<true>)
   unsigned* gt_best;         // (N, Gmax) IoU bits, zeroed by the call
 };
 
@@ -68,6 +69,8 @@ __device__ __forceinline__ int compact_round(const float* a, float ra, bool live
 // Pass 1 (anchor_match1_rot_kernel of detection_ops.hip per image + the targets): per-anchor best IoU / matched box in LDS words and
 // registers only, per-box best over all anchors into gt_best.  Writes the deltas (they depend on the match alone) and either the final
 // label or, when pass 2 follows for the image, the match packed with the threshold label: (match << 2) | (label + 1).
+// BOXES: the matched gt box instead of its deltas (zeros for an image without gts, as the deltas).
+template <bool BOXES>
 __global__ __launch_bounds__(256) void retina_label1_rot_kernel(const LabelArgs a) {
   extern __shared__ unsigned lbest[];   // [Gmax]
   __shared__ unsigned pairs[256 * RR_GS];
@@ -117,14 +120,19 @@ __global__ __launch_bounds__(256) void retina_label1_rot_kernel(const LabelArgs 
         const int m = (int)(0xFFFFFFFFu - (unsigned)(bb & 0xFFFFFFFFull));
         const int ml = (v < a.lo) ? a.l0 : ((v < a.hi) ? a.l1 : a.l2);
         lab = a.low_quality ? ((m << 2) | (ml + 1)) : class_of(ml, a.num_classes, cls, m);
-        const float* t = gts + m * 5;     // Box2BoxTransformRotated.get_deltas, as get_deltas_kernel of rcnn_ops.hip
-        d[0] = a.w.w[0] * (t[0] - s[0]) / s[2]; d[1] = a.w.w[1] * (t[1] - s[1]) / s[3];
-        d[2] = a.w.w[2] * logf(t[2] / s[2]); d[3] = a.w.w[3] * logf(t[3] / s[3]);
-        float da = t[4] - s[4];
-        da = fmodf(da + 180.f, 360.f);
-        if (da < 0.f) da += 360.f;            // python's % (result takes the sign of the divisor)
-        da -= 180.f;
-        d[4] = da * a.w.w[4] * RR_PI / 180.f;
+        const float* t = gts + m * 5;
+        if constexpr (BOXES) {
+#pragma unroll
+          for (int e = 0; e < 5; ++e) d[e] = t[e];
+        } else {                          // Box2BoxTransformRotated.get_deltas, as get_deltas_kernel of rcnn_ops.hip
+          d[0] = a.w.w[0] * (t[0] - s[0]) / s[2]; d[1] = a.w.w[1] * (t[1] - s[1]) / s[3];
+          d[2] = a.w.w[2] * logf(t[2] / s[2]); d[3] = a.w.w[3] * logf(t[3] / s[3]);
+          float da = t[4] - s[4];
+          da = fmodf(da + 180.f, 360.f);
+          if (da < 0.f) da += 360.f;          // python's % (result takes the sign of the divisor)
+          da -= 180.f;
+          d[4] = da * a.w.w[4] * RR_PI / 180.f;
+        }
       }
       labels[i] = lab;
 #pragma unroll
@@ -311,10 +319,11 @@ inline bool matcher_label(int l) { return l >= -1 && l <= 1; }
 
 }  // namespace
 
-extern "C" int sod_retina_label_rotated(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts, int N,
-                                        int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
-                                        int allow_low_quality, int num_classes, const float* weights5, int* gt_labels, float* gt_deltas,
-                                        unsigned* gt_best_ws, void* stream) {
+template <bool BOXES>
+static int label_rotated(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts, int N,
+                         int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
+                         int allow_low_quality, int num_classes, const float* weights5, int* gt_labels, float* gt_deltas,
+                         unsigned* gt_best_ws, void* stream) {
   LabelArgs a{};
   if (!anchors || R <= 0 || !gt_counts || N <= 0 || N > 65535 || Gmax < 0 || Gmax > SOD_RETINA_LABEL_MAX_GT || num_classes <= 0 || !gt_labels || !gt_deltas ||
       !fill_w5(a.w, weights5) || !matcher_label(label_below) || !matcher_label(label_between) || !matcher_label(label_above))
@@ -332,10 +341,26 @@ extern "C" int sod_retina_label_rotated(const float* anchors, int R, const float
   a.num_classes = num_classes; a.labels = gt_labels; a.deltas = gt_deltas; a.gt_best = gt_best_ws;
   const dim3 grid(rr_nblk(R, 2048), N);
   const size_t lds = sizeof(unsigned) * (Gmax > 0 ? Gmax : 1);
-  SOD_LAUNCH(retina_label1_rot_kernel, grid, dim3(256), lds, st, a);
+  SOD_LAUNCH(retina_label1_rot_kernel<BOXES>, grid, dim3(256), lds, st, a);
   if (a.low_quality) SOD_LAUNCH(retina_label2_rot_kernel, grid, dim3(256), lds, st, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
+}
+
+extern "C" int sod_retina_label_rotated(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts, int N,
+                                        int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
+                                        int allow_low_quality, int num_classes, const float* weights5, int* gt_labels, float* gt_deltas,
+                                        unsigned* gt_best_ws, void* stream) {
+  return label_rotated<false>(anchors, R, gt_boxes, gt_classes, gt_counts, N, Gmax, thr_lo, thr_hi, label_below, label_between, label_above,
+                              allow_low_quality, num_classes, weights5, gt_labels, gt_deltas, gt_best_ws, stream);
+}
+
+extern "C" int sod_retina_label_rotated_boxes(const float* anchors, int R, const float* gt_boxes, const int* gt_classes, const int* gt_counts,
+                                              int N, int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
+                                              int allow_low_quality, int num_classes, const float* weights5, int* gt_labels,
+                                              float* matched_boxes, unsigned* gt_best_ws, void* stream) {
+  return label_rotated<true>(anchors, R, gt_boxes, gt_classes, gt_counts, N, Gmax, thr_lo, thr_hi, label_below, label_between, label_above,
+                             allow_low_quality, num_classes, weights5, gt_labels, matched_boxes, gt_best_ws, stream);
 }
 
 static int box5_fill(Box5Args& a, const float* pred, int pitch, const int* labels, const float* deltas, int N, int R, int A, int K, float beta) {

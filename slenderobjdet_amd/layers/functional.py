@@ -1386,10 +1386,12 @@ def retina_box_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes,
 
 
 # ----------------------------------------------------------------------------------------------- RotatedRetinaNet
-def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, labels, allow_low_quality, num_classes, weights, ws=None):
+def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, labels, allow_low_quality, num_classes, weights, ws=None,
+                         want_boxes=False):
     """label_anchors of the whole batch in two launches: anchors (R, 5), gt_boxes (N, Gmax, 5) / gt_classes (N, Gmax) int32 padded,
     gt_counts (N) int32 on the device (never read back) -> gt_labels (N, R) int32 in {-1, 0..K-1, K}, gt_deltas (N, R, 5).  ``ws``: N * Gmax
-    int32 words (zeroed by the call); allocated when None."""
+    int32 words (zeroed by the call); allocated when None.  ``want_boxes``: the second output holds the matched gt box of every anchor
+    instead of its deltas (what the rotated IoU loss compares with); the labels are the same."""
     _chk(anchors, torch.float32, "anchors"); _chk(gt_boxes, torch.float32, "gt_boxes"); _chk(gt_classes, torch.int32, "gt_classes")
     _chk(gt_counts, torch.int32, "gt_counts")
     R = anchors.shape[0]
@@ -1405,7 +1407,7 @@ def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, l
     gt_labels = torch.empty((N, R), dtype=torch.int32, device=dev)
     gt_deltas = torch.empty((N, R, 5), dtype=torch.float32, device=dev)
     w = _float_arr(weights)
-    call("sod_retina_label_rotated", ptr(anchors), R, ptr(gt_boxes) if Gmax else None, ptr(gt_classes) if Gmax else None, ptr(gt_counts), N, Gmax,
+    call("sod_retina_label_rotated_boxes" if want_boxes else "sod_retina_label_rotated", ptr(anchors), R, ptr(gt_boxes) if Gmax else None, ptr(gt_classes) if Gmax else None, ptr(gt_counts), N, Gmax,
          float(thresholds[0]), float(thresholds[1]), int(labels[0]), int(labels[1]), int(labels[2]), 1 if allow_low_quality else 0, int(num_classes),
          ctypes.cast(w, ctypes.c_void_p), ptr(gt_labels), ptr(gt_deltas), ptr(ws), stream_ptr())
     return gt_labels, gt_deltas
@@ -1421,6 +1423,59 @@ def retina_box5_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes
 def retina_box5_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, grad_num, grad_den, dpred):
     call("sod_retina_box5_loss_bwd_f32" if is_f32() else "sod_retina_box5_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta),
          ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
+
+
+def rotated_iou_loss_fwd(pred, target, want_elem=True):
+    """1 - IoU of the pairs (pred[i], target[i]) of (P, 5) boxes (cx, cy, w, h, angle_deg) -> (elem (P) or None, sum (1)); the IoU is
+    box_iou_rotated's, to the bit."""
+    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target")
+    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
+        raise _C.SlenderHipError("rotated_iou_loss: pred and target must both be (P, 5)")
+    P = pred.shape[0]
+    elem = torch.empty(P, dtype=torch.float32, device=pred.device) if want_elem else None
+    s = torch.empty(1, dtype=torch.float32, device=pred.device)
+    call("sod_rotated_iou_loss", ptr(pred), ptr(target), P, ptr(elem), ptr(s), None, None, ptr(reduce_ws(pred.device)), stream_ptr())
+    return elem, s
+
+
+def rotated_iou_loss_bwd(pred, target, grad_scale=None):
+    """grad_scale[0] * d sum(1 - IoU) / d pred (P, 5), the angle's column per degree; rows without overlap (IoU exactly 0) are zero."""
+    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target"); _chk(grad_scale, torch.float32, "grad_scale")
+    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
+        raise _C.SlenderHipError("rotated_iou_loss: pred and target must both be (P, 5)")
+    d = torch.empty_like(pred)
+    call("sod_rotated_iou_loss", ptr(pred), ptr(target), pred.shape[0], None, None, ptr(grad_scale), ptr(d), None, stream_ptr())
+    return d
+
+
+def _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights):
+    """The kernels index by N, R, A and pitch alone: the buffers must have exactly those sizes."""
+    _chk(pred, torch.float32, "pred"); _chk(gt_labels, torch.int32, "gt_labels"); _chk(anchors, torch.float32, "anchors")
+    _chk(matched_boxes, torch.float32, "matched_boxes")
+    if (len(weights) != 5 or A <= 0 or R % A or pitch < A * 5 or pred.numel() != N * (R // A) * pitch or gt_labels.numel() != N * R
+            or tuple(anchors.shape) != (R, 5) or matched_boxes.numel() != N * R * 5):
+        raise _C.SlenderHipError("retina_riou_loss: pred (N, R / A, pitch >= A * 5), gt_labels (N, R), anchors (R, 5), matched_boxes (N, R, 5), five weights")
+
+
+def retina_riou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
+    """Rotated IoU box regression of RotatedRetinaNet on the pitched delta buffer (five deltas per anchor); advances the EMA normaliser;
+    returns [sum of 1 - IoU over the positives, num_pos]."""
+    _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights)
+    sums = torch.empty(2, dtype=torch.float32, device=pred.device)
+    w = _float_arr(weights)
+    call("sod_retina_riou_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
+         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(sums), ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
+    return sums
+
+
+def retina_riou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
+    _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights)
+    _chk(dpred, ACT_DTYPE, "dpred")
+    if dpred.numel() != pred.numel():
+        raise _C.SlenderHipError("retina_riou_loss: dpred must have the prediction buffer's shape")
+    w = _float_arr(weights)
+    call("sod_retina_riou_loss_bwd_f32" if is_f32() else "sod_retina_riou_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
+         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
 
 
 def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):

@@ -2,6 +2,7 @@
 
   sigmoid_focal_loss(_jit)  — fvcore.nn.sigmoid_focal_loss_jit as called at slender_det/modeling/meta_arch/fcos/fcosv2.py:124
   iou_loss                  — slender_det/layers/iou_loss.py:4-37
+  rotated_iou_loss          — 1 - IoU of rotated box pairs (no counterpart in the reference), csrc/rotated_iou_loss.hip
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -97,3 +98,38 @@ class _BceSoftFn(torch.autograd.Function):
 
 def bce_with_logits_fg_sum(logits, targets, labels, bg_label):
     return _BceSoftFn.apply(logits, targets, labels, bg_label)
+
+
+class _RotatedIouLossFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, pred, target, reduction):
+        p, t = pred.contiguous().float(), target.contiguous().float()
+        elem, s = HF.rotated_iou_loss_fwd(p, t, want_elem=(reduction == "none"))
+        ctx.save_for_backward(p, t)
+        ctx.reduction = reduction
+        if reduction == "none":
+            return elem.view(pred.shape[:-1])
+        return s[0] / max(p.shape[0], 1) if reduction == "mean" else s[0]
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        p, t = ctx.saved_tensors
+        if ctx.reduction == "none":
+            return HF.rotated_iou_loss_bwd(p, t) * g.reshape(-1, 1).float(), None, None
+        scale = g.reshape(1).float().contiguous()
+        if ctx.reduction == "mean":
+            scale = scale / max(p.shape[0], 1)
+        return HF.rotated_iou_loss_bwd(p, t, grad_scale=scale), None, None
+
+
+def rotated_iou_loss(pred, target, reduction="sum"):
+    """1 - IoU(pred, target) of (P, 5) rotated boxes (cx, cy, w, h, angle_deg), the IoU being box_iou_rotated's (detectron2's); the
+    gradient flows to ``pred`` only, its angle column per degree.  Boxes that do not overlap (IoU exactly 0) have loss 1 and NO gradient:
+    use it on matched pairs (a positive anchor and its gt), not to pull distant boxes together.  The IoU has kinks where a vertex of one
+    box lies on an edge of the other and at identical boxes; the gradient there is the one of a side."""
+    if reduction not in ("sum", "mean", "none"):
+        raise ValueError(f"rotated_iou_loss: reduction must be 'sum', 'mean' or 'none', got {reduction!r}")
+    if pred.dim() != 2 or pred.shape[-1] != 5 or pred.shape != target.shape:
+        raise ValueError(f"rotated_iou_loss: pred and target must both be (P, 5), got {tuple(pred.shape)} and {tuple(target.shape)}")
+    return _RotatedIouLossFn.apply(pred, target, reduction)

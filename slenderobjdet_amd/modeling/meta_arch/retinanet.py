@@ -103,6 +103,9 @@ class _RetinaLossFn(torch.autograd.Function):
         if model.box_reg_loss_type == "giou":       # gt_deltas then holds the matched gt BOXES (N,R,4)
             sums = HF.retina_giou_loss_fwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
                                            model.scale_clamp, model.loss_normalizer, model.loss_normalizer_momentum)
+        elif model.box_reg_loss_type == "rotated_iou":      # RotatedRetinaNet: gt_deltas holds the matched gt BOXES (N,R,5)
+            sums = HF.retina_riou_loss_fwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
+                                           model.scale_clamp, model.loss_normalizer, model.loss_normalizer_momentum)
         else:
             box_loss_fwd = HF.retina_box5_loss_fwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_fwd
             sums = box_loss_fwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta,
@@ -150,6 +153,9 @@ class _RetinaLossFn(torch.autograd.Function):
         if model.box_reg_loss_type == "giou":
             HF.retina_giou_loss_bwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
                                     model.scale_clamp, g2[1:2], norm, dbox)
+        elif model.box_reg_loss_type == "rotated_iou":
+            HF.retina_riou_loss_bwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
+                                    model.scale_clamp, g2[1:2], norm, dbox)
         else:
             box_loss_bwd = HF.retina_box5_loss_bwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_bwd
             box_loss_bwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta, g2[1:2], norm, dbox)
@@ -190,8 +196,9 @@ class RetinaNetBase(nn.Module):
         self.focal_loss_alpha, self.focal_loss_gamma = r.FOCAL_LOSS_ALPHA, r.FOCAL_LOSS_GAMMA
         self.smooth_l1_loss_beta = r.SMOOTH_L1_LOSS_BETA
         self.box_reg_loss_type = r.BBOX_REG_LOSS_TYPE
-        if self.box_reg_loss_type not in ("smooth_l1", "giou"):
-            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")          # retina_rotated.py:243-244
+        if self.box_reg_loss_type not in self.box_reg_loss_types:
+            raise ValueError(f"{type(self).__name__}: MODEL.RETINANET.BBOX_REG_LOSS_TYPE must be one of {self.box_reg_loss_types}, "
+                             f"got {self.box_reg_loss_type!r}")                                 # retina_rotated.py:243-244
         self.scale_clamp = math.log(1000.0 / 16)
         self.iou_thresholds, self.iou_labels = list(r.IOU_THRESHOLDS), list(r.IOU_LABELS)
         self.bbox_reg_weights = tuple(r.BBOX_REG_WEIGHTS)
@@ -212,6 +219,7 @@ class RetinaNetBase(nn.Module):
         self._anchor_cache = {}
 
     box_dim = 4
+    box_reg_loss_types = ("smooth_l1", "giou")
 
     @staticmethod
     def num_cell_anchors(cfg):

@@ -5,8 +5,10 @@ synthetic batches, bench.train_step with prefetch and the reference's warm-up sc
     on the same inputs, the two alternating; the labels of the two are compared first;
   * img/s of a full training step of the three classes, built one after the other in this process.
 Device events, warm-up, >= 20 timed calls; prints the card's shader clock with the figures.
+``--box-loss rotated_iou`` trains RotatedRetinaNet's box regression with the rotated IoU loss (MODEL.RETINANET.BBOX_REG_LOSS_TYPE)
+instead of smooth-L1; ``--rotated-only`` times RotatedRetinaNet's step alone (alternating runs of the two box losses, one process each).
 
-    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--out FILE]
+    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--box-loss smooth_l1|rotated_iou] [--rotated-only] [--out FILE]
 """
 import argparse
 import json
@@ -28,6 +30,8 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--calls", type=int, default=20, help="timed calls per round of the labelling comparison (three rounds)")
 ap.add_argument("--skip-step", action="store_true", help="only the labelling comparison")
+ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou"], default="smooth_l1", help="RotatedRetinaNet's box regression loss")
+ap.add_argument("--rotated-only", action="store_true", help="time RotatedRetinaNet's training step only, not the two other classes")
 ap.add_argument("--out", default=None, help="also write the JSON result to this file")
 args = ap.parse_args()
 
@@ -50,11 +54,12 @@ def rotated_retina_cfg():
     ag = cfg.MODEL.ANCHOR_GENERATOR
     ag.NAME, ag.SIZES, ag.ASPECT_RATIOS, ag.ANGLES = "RotatedAnchorGenerator", SIZES, RATIOS, ANGLES
     cfg.MODEL.RETINANET.BBOX_REG_WEIGHTS = W5
+    cfg.MODEL.RETINANET.BBOX_REG_LOSS_TYPE = args.box_loss
     return cfg
 
 
 assert sum(h * w for h, w in level_hw) == 22400
-out = {"geometry": {"batch": N, "padded": [Hp, Wp], "level_hw": level_hw}, "device": device_fingerprint(0)}
+out = {"geometry": {"batch": N, "padded": [Hp, Wp], "level_hw": level_hw}, "device": device_fingerprint(0), "box_loss": args.box_loss}
 
 # ---------------------------------------------------------------------------------------------- labelling
 anchors = torch.cat(grid_anchors_rotated(level_hw, strides, SIZES, RATIOS, ANGLES, 0.0, dev)).contiguous()
@@ -124,8 +129,9 @@ print(f"labelling N = {N}, R = {R}, {sum(counts)} gts (max {Gmax}): fused {sum(t
 
 # ---------------------------------------------------------------------------------------------- training steps
 if not args.skip_step:
-    for arch, cfg, rotated in (("RotatedRetinaNet", rotated_retina_cfg(), True), ("RetinaNet", make_cfg(50, "retinanet"), False),
-                               ("GeneralizedRCNN+RRPN+RROIHeads", make_cfg(50, "rrcnn"), True)):
+    classes = (("RotatedRetinaNet", rotated_retina_cfg(), True), ("RetinaNet", make_cfg(50, "retinanet"), False),
+               ("GeneralizedRCNN+RRPN+RROIHeads", make_cfg(50, "rrcnn"), True))
+    for arch, cfg, rotated in classes[:1] if args.rotated_only else classes:
         torch.manual_seed(1)
         model = build_model(cfg)
         model.train()
