@@ -574,7 +574,12 @@ int sod_f32_to_bf16(const float* x, void* y, long long n, void* stream);
  * sod_retina_targets = tail of label_anchors (:279-291) + Box2BoxTransform.get_deltas (:203-206) for ONE image (weights4 host);
  * sod_retina_box_loss_* = smooth_l1_loss(pred_deltas[pos], gt_deltas[pos], beta, "sum") (:229) on the pitched prediction buffer
  * (anchor a of pixel p at p*pitch + a*4) + the EMA loss normaliser (:210-214) kept on the device:
- * normalizer <- momentum*normalizer + (1-momentum)*max(num_pos,1); sums2 = {loss sum, num_pos}. */
+ * normalizer <- momentum*normalizer + (1-momentum)*max(num_pos,1); sums2 = {loss sum, num_pos}.
+ * The contract of all four fused box losses (csrc/retina_box_loss.hip: sod_retina_{box,box5,giou,riou}_loss_*, D = 4, 5, 4, 5 deltas per
+ * anchor), said once: pred and dpred are (N, R / A, pitch) with pitch >= A*D, gt_labels (N, R), the target (N, R, D); the sizes are not
+ * checked beyond that (the caller's job); positives are 0 <= label != num_classes.  bwd writes EVERY element of every pixel's pitch-wide
+ * row of dpred (bf16, or fp32 for *_bwd_f32): grad_num[0] / grad_den[0] * d sum / d pred in the D columns of a positive, exact zeros in
+ * the columns of every other anchor and in the pad columns [A*D, pitch) - no pre-zeroed buffer is needed. */
 int sod_retina_targets(const float* anchors, int A, const float* gt_boxes, const int* gt_classes, int G, const int* matches,
                        const signed char* match_labels, int num_classes, const float* weights4, int* gt_labels, float* gt_deltas,
                        void* stream);
@@ -725,7 +730,8 @@ int sod_fcos_rpd_finalize(const float* focal_sum, const float* iou_sum, const fl
 
 /* BBOX_REG_LOSS_TYPE "giou" of RetinaNet (retina_rotated.py:236-245) and AnchorHead (meta/heads/anchor_head.py:366-374): positives decode
  * their deltas against the anchor (Box2BoxTransform.apply_deltas) and take fvcore giou_loss (eps 1e-7) against the matched gt box
- * (matched_boxes (N,R,4)); same sums2 / EMA-normaliser / pitched bf16 gradient contract as sod_retina_box_loss_*. */
+ * (matched_boxes (N,R,4)); sums2, the EMA normaliser and the pitched gradient (pad columns included): see sod_retina_box_loss_*.
+ * A NaN delta stays a NaN loss here (dw > clamp ? clamp : dw), unlike sod_box2box_apply_deltas, whose fminf drops a NaN dw / dh. */
 int sod_retina_giou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
                              int N, int R, int A, int num_classes, const float* weights4, float scale_clamp, float* sums2,
                              float* normalizer, float momentum, float* ws, void* stream);
@@ -896,7 +902,8 @@ int sod_coco_match_rotated(const int* gt_off, const float* gt_box5, const unsign
  *   -1 -> -1, 1 -> class of the matched gt; gt_deltas (N, R, 5) = Box2BoxTransformRotated.get_deltas(anchor, matched gt) (weights5 host);
  *   an image without gts: all num_classes / all 0.  gt_best_ws: N * Gmax unsigned words, zeroed by the call.  Labels and matches are
  *   identical to sod_anchor_match_rotated + sod_retina_targets' mapping per image.  Gmax <= SOD_RETINA_LABEL_MAX_GT (LDS), N <= 65535.
- * sod_retina_box5_loss_*: sod_retina_box_loss_* for 5 deltas per anchor (anchor a of pixel p at p*pitch + a*5, pitch >= A*5).
+ * sod_retina_box5_loss_*: sod_retina_box_loss_* for 5 deltas per anchor (anchor a of pixel p at p*pitch + a*5, pitch >= A*5); the
+ *   contract, pad columns included, is stated there.
  * sod_retina_decode_rotated: Box2BoxTransformRotated.apply_deltas for the candidates of sod_dense_topk_select in one launch: slot (n, m)
  *   of level m / top_n holds level-local row rows[n, m]; anchor = row + level_row0[level] (host array, nlev <= 8, M = nlev * top_n);
  *   out (N, M, 5); a slot whose score is -inf or whose box is not finite gets five zeros; the rest is bit-equal to
@@ -931,8 +938,7 @@ int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors
  *   arithmetic of sod_box2box_apply_deltas (box_dim 5; dw, dh clamped at scale_clamp, angle wrapped into [-180, 180)) and take the pair
  *   loss against matched_boxes (N, R, 5).  fwd: sums2 = [sum, number of positives], normalizer <- m*normalizer + (1-m)*max(npos, 1).
  *   bwd: dpred = grad_num[0] / grad_den[0] * d sum / d pred through the decode (d cx / d dx = aw / wx, d w / d dw = w / ww and 0 where
- *   the clamp is active, d angle_deg / d da = 180 / (pi * wa)); the five columns of every non-positive anchor and the pad columns
- *   [A*5, pitch) are written as exact zeros.
+ *   the clamp is active, d angle_deg / d da = 180 / (pi * wa)); which elements of dpred are written: see sod_retina_box_loss_*.
  * sod_retina_label_rotated_boxes: sod_retina_label_rotated (same kernels, one template switch, identical labels) writing
  *   matched_boxes (N, R, 5) = gt_boxes[n, match] for EVERY anchor instead of the deltas; zeros for an image without gts. */
 int sod_rotated_iou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,

@@ -62,6 +62,30 @@ __device__ __forceinline__ float block_sum_256(float v, float* red /* >=4 floats
   return red[0] + red[1] + red[2] + red[3];
 }
 
+// ---- the reduction tail of every loss kernel: per-block partials, then one block adds them in index order (the same bits from run to run)
+constexpr int SOD_RED = 1024;      // max partials per reduced scalar: scalar s of a reduction keeps its partials at part[s * SOD_RED + block]
+
+inline int sod_nblk(long long n, int cap = SOD_RED) {      // 256-thread blocks for n items, between 1 and cap
+  long long g = (n + 255) / 256;
+  if (g > cap) g = cap;
+  if (g < 1) g = 1;
+  return (int)g;
+}
+
+// out[s] (+)= sum of part[s * SOD_RED + 0 .. nblk): thread t adds i = t, t + 256, ... in order, then block_sum_256.  One block of 256.
+// (A template - launched as sod_finish_sums_kernel<> - so that only the translation units that launch it get a copy.)
+template <int = 0>
+__global__ void sod_finish_sums_kernel(const float* __restrict__ part, int nblk, int nscalars, float* __restrict__ out, int accumulate) {
+  __shared__ float red[4];
+  for (int s = 0; s < nscalars; ++s) {
+    float v = 0.f;
+    for (int i = threadIdx.x; i < nblk; i += 256) v += part[s * SOD_RED + i];
+    v = block_sum_256(v, red);
+    if (threadIdx.x == 0) out[s] = accumulate ? out[s] + v : v;
+    __syncthreads();
+  }
+}
+
 // detectron2 pairwise_iou of two XYXY boxes, as the matchers evaluate it (sod_anchor_match in detection_ops.hip and the batched
 // sod_fcos_rpd_refine_targets in fcos_rpd.hip give bit-identical values: one definition)
 __device__ __forceinline__ float pair_iou(const float* g, const float* a) {

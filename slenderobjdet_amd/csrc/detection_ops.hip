@@ -12,6 +12,8 @@
 namespace {
 
 #include "rotated_iou.h"
+#include "box_transform.h"      // xyxy_get_deltas
+#include "box_pair_loss.h"      // giou_pair
 
 __global__ __launch_bounds__(256) void pairwise_iou_rotated_kernel(const float* __restrict__ b1, int n1, const float* __restrict__ b2, int n2,
                                                                    float* __restrict__ out) {
@@ -243,15 +245,6 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tile_kernel(const RoiArgs a
 }
 
 // ---------------------------------------------------------------------------------------------- box losses on XYXY
-constexpr int RED = 1024;
-__global__ void finish_sum2(const float* __restrict__ part, int nblk, float* __restrict__ out) {
-  __shared__ float red[4];
-  float v = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += 256) v += part[i];
-  v = block_sum_256(v, red);
-  if (threadIdx.x == 0) out[0] = v;
-}
-
 // fvcore giou_loss (eps 1e-7): per-row loss and gradient w.r.t. boxes1
 __global__ __launch_bounds__(256) void giou_xyxy_kernel(const float* __restrict__ b1, const float* __restrict__ b2, long long P, float eps,
                                                         float* __restrict__ elem, float* __restrict__ part, const float* __restrict__ gscale,
@@ -261,35 +254,11 @@ __global__ __launch_bounds__(256) void giou_xyxy_kernel(const float* __restrict_
   const float gs = gscale ? gscale[0] : 1.f;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) {
     const f32x4_t a = *reinterpret_cast<const f32x4_t*>(b1 + i * 4), b = *reinterpret_cast<const f32x4_t*>(b2 + i * 4);
-    const float x1 = a[0], y1 = a[1], x2 = a[2], y2 = a[3], x1g = b[0], y1g = b[1], x2g = b[2], y2g = b[3];
-    const float xk1 = fmaxf(x1, x1g), yk1 = fmaxf(y1, y1g), xk2 = fminf(x2, x2g), yk2 = fminf(y2, y2g);
-    const bool ov = (yk2 > yk1) && (xk2 > xk1);
-    const float inter = ov ? (xk2 - xk1) * (yk2 - yk1) : 0.f;
-    const float uni = (x2 - x1) * (y2 - y1) + (x2g - x1g) * (y2g - y1g) - inter;
-    const float iou = inter / (uni + eps);
-    const float xc1 = fminf(x1, x1g), yc1 = fminf(y1, y1g), xc2 = fmaxf(x2, x2g), yc2 = fmaxf(y2, y2g);
-    const float ac = (xc2 - xc1) * (yc2 - yc1);
-    const float l = 1.f - (iou - (ac - uni) / (ac + eps));
+    float g[4];
+    const float l = giou_pair(a, b, eps, d1 ? g : nullptr);
     if (elem) elem[i] = l;
     acc += l;
-    if (d1) {
-      // derivatives of inter / union / hull w.r.t. (x1,y1,x2,y2) of box 1; max/min ties split like torch
-      auto dmax = [](float p, float q) { return p > q ? 1.f : (p == q ? 0.5f : 0.f); };
-      auto dmin = [](float p, float q) { return p < q ? 1.f : (p == q ? 0.5f : 0.f); };
-      const float iw = xk2 - xk1, ih = yk2 - yk1, w1 = x2 - x1, h1 = y2 - y1, cw = xc2 - xc1, ch = yc2 - yc1;
-      const float di[4] = {ov ? -dmax(x1, x1g) * ih : 0.f, ov ? -dmax(y1, y1g) * iw : 0.f, ov ? dmin(x2, x2g) * ih : 0.f, ov ? dmin(y2, y2g) * iw : 0.f};
-      const float da[4] = {-h1, -w1, h1, w1};
-      const float dc[4] = {-dmin(x1, x1g) * ch, -dmin(y1, y1g) * cw, dmax(x2, x2g) * ch, dmax(y2, y2g) * cw};
-      f32x4_t g;
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float du = da[e] - di[e];
-        const float diou = (di[e] * (uni + eps) - inter * du) / ((uni + eps) * (uni + eps));
-        const float dterm = ((dc[e] - du) * (ac + eps) - (ac - uni) * dc[e]) / ((ac + eps) * (ac + eps));
-        g[e] = -(diou - dterm) * gs;
-      }
-      *reinterpret_cast<f32x4_t*>(d1 + i * 4) = g;
-    }
+    if (d1) *reinterpret_cast<f32x4_t*>(d1 + i * 4) = f32x4_t{g[0] * gs, g[1] * gs, g[2] * gs, g[3] * gs};
   }
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0 && part) part[blockIdx.x] = acc;
@@ -444,7 +413,7 @@ __global__ __launch_bounds__(256) void anchor_match2_kernel(const float* __restr
   }
 }
 
-// ---------------------------------------------------------------------------------------------- RetinaNet targets / box loss
+// ---------------------------------------------------------------------------------------------- RetinaNet targets (the box loss: retina_box_loss.hip)
 // label_anchors tail (retina_rotated.py:279-291) + Box2BoxTransform.get_deltas for one image
 __global__ __launch_bounds__(256) void retina_targets_kernel(const float* __restrict__ anchors, int A, const float* __restrict__ gts,
                                                              const int* __restrict__ gt_classes, int G, const int* __restrict__ matches,
@@ -459,163 +428,14 @@ __global__ __launch_bounds__(256) void retina_targets_kernel(const float* __rest
       lab = (ml == 0) ? num_classes : ((ml == -1) ? -1 : gt_classes[m]);
       const f32x4_t s = *reinterpret_cast<const f32x4_t*>(anchors + (long long)i * 4);
       const f32x4_t t = *reinterpret_cast<const f32x4_t*>(gts + (long long)m * 4);
-      const float sw = s[2] - s[0], sh = s[3] - s[1], scx = s[0] + 0.5f * sw, scy = s[1] + 0.5f * sh;
-      const float tw = t[2] - t[0], th = t[3] - t[1], tcx = t[0] + 0.5f * tw, tcy = t[1] + 0.5f * th;
-      d = f32x4_t{wx * (tcx - scx) / sw, wy * (tcy - scy) / sh, ww * logf(tw / sw), wh * logf(th / sh)};
+      const float w[4] = {wx, wy, ww, wh};
+      float o[4];
+      xyxy_get_deltas(s, t, w, o);
+      d = f32x4_t{o[0], o[1], o[2], o[3]};
     }
     gt_labels[i] = lab;
     *reinterpret_cast<f32x4_t*>(deltas + (long long)i * 4) = d;
   }
-}
-
-struct RetinaBoxArgs {
-  const float* pred;        // (N, sumHW, pitch) fp32: anchor a of pixel p at p*pitch + a*4
-  const int* labels;        // (N, R)
-  const float* deltas;      // (N, R, 4)
-  int N, R, A, pitch, num_classes;
-  float beta;
-};
-
-template <bool BWD, typename T = __bf16>      // T: storage type of the delta gradient (bf16 product path, float in the fp32 validation mode)
-__global__ __launch_bounds__(256) void retina_box_kernel(const RetinaBoxArgs a, float* __restrict__ part, const float* __restrict__ gnum,
-                                                         const float* __restrict__ gden, T* __restrict__ dpred) {
-  __shared__ float red[4];
-  float acc = 0.f, npos = 0.f;
-  const float sc = BWD ? gnum[0] / gden[0] : 0.f;
-  const long long total = (long long)a.N * a.R;
-  const long long pix_per_img = a.R / a.A;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long n = i / a.R, r = i - n * a.R;
-    const long long px = r / a.A;
-    const int an = (int)(r - px * a.A);
-    const long long po = (n * pix_per_img + px) * a.pitch + an * 4;
-    const int lab = a.labels[i];
-    const bool pos = lab >= 0 && lab != a.num_classes;
-    f32x4_t g = {0.f, 0.f, 0.f, 0.f};
-    if (pos) {
-      npos += 1.f;
-      const f32x4_t p = *reinterpret_cast<const f32x4_t*>(a.pred + po), t = *reinterpret_cast<const f32x4_t*>(a.deltas + i * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        const float d = p[e] - t[e], ad = fabsf(d);
-        if (a.beta < 1e-5f) { acc += ad; g[e] = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-        else if (ad < a.beta) { acc += 0.5f * d * d / a.beta; g[e] = d / a.beta; }
-        else { acc += ad - 0.5f * a.beta; g[e] = d > 0.f ? 1.f : -1.f; }
-      }
-    }
-    if (BWD) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dpred[po + e] = (T)(g[e] * sc);
-    }
-  }
-  if (!BWD) {
-    acc = block_sum_256(acc, red);
-    npos = block_sum_256(npos, red);
-    if (threadIdx.x == 0) { part[blockIdx.x] = acc; part[RED + blockIdx.x] = npos; }
-  }
-}
-
-// fvcore giou_loss of ONE pair and its gradient w.r.t. the first box (same arithmetic as giou_xyxy_kernel)
-__device__ __forceinline__ float giou_pair(const float* a, const float* b, float eps, float* g /* may be null */) {
-  const float x1 = a[0], y1 = a[1], x2 = a[2], y2 = a[3], x1g = b[0], y1g = b[1], x2g = b[2], y2g = b[3];
-  const float xk1 = fmaxf(x1, x1g), yk1 = fmaxf(y1, y1g), xk2 = fminf(x2, x2g), yk2 = fminf(y2, y2g);
-  const bool ov = (yk2 > yk1) && (xk2 > xk1);
-  const float inter = ov ? (xk2 - xk1) * (yk2 - yk1) : 0.f;
-  const float uni = (x2 - x1) * (y2 - y1) + (x2g - x1g) * (y2g - y1g) - inter;
-  const float iou = inter / (uni + eps);
-  const float xc1 = fminf(x1, x1g), yc1 = fminf(y1, y1g), xc2 = fmaxf(x2, x2g), yc2 = fmaxf(y2, y2g);
-  const float ac = (xc2 - xc1) * (yc2 - yc1);
-  if (g) {
-    auto dmax = [](float p, float q) { return p > q ? 1.f : (p == q ? 0.5f : 0.f); };
-    auto dmin = [](float p, float q) { return p < q ? 1.f : (p == q ? 0.5f : 0.f); };
-    const float iw = xk2 - xk1, ih = yk2 - yk1, w1 = x2 - x1, h1 = y2 - y1, cw = xc2 - xc1, ch = yc2 - yc1;
-    const float di[4] = {ov ? -dmax(x1, x1g) * ih : 0.f, ov ? -dmax(y1, y1g) * iw : 0.f, ov ? dmin(x2, x2g) * ih : 0.f, ov ? dmin(y2, y2g) * iw : 0.f};
-    const float da[4] = {-h1, -w1, h1, w1};
-    const float dc[4] = {-dmin(x1, x1g) * ch, -dmin(y1, y1g) * cw, dmax(x2, x2g) * ch, dmax(y2, y2g) * cw};
-#pragma unroll
-    for (int e = 0; e < 4; ++e) {
-      const float du = da[e] - di[e];
-      const float diou = (di[e] * (uni + eps) - inter * du) / ((uni + eps) * (uni + eps));
-      const float dterm = ((dc[e] - du) * (ac + eps) - (ac - uni) * dc[e]) / ((ac + eps) * (ac + eps));
-      g[e] = -(diou - dterm);
-    }
-  }
-  return 1.f - (iou - (ac - uni) / (ac + eps));
-}
-
-// RetinaNet BBOX_REG_LOSS_TYPE "giou" (retina_rotated.py:236-245; AnchorHead, meta/heads/anchor_head.py:366-374): positives decode
-// their deltas against the anchor (Box2BoxTransform.apply_deltas) and take giou_loss against the matched gt box; backward chains
-// d(giou)/d(box) through the decode into the pitched bf16 delta gradient.
-struct RetinaGiouArgs {
-  const float* pred; const int* labels; const float* anchors; const float* gt; // pred (N,P,pitch), labels (N,R), anchors (R,4), gt (N,R,4)
-  int N, R, A, pitch, num_classes;
-  float wx, wy, ww, wh, clampv;
-};
-template <bool BWD, typename T = __bf16>
-__global__ __launch_bounds__(256) void retina_giou_kernel(const RetinaGiouArgs a, float* __restrict__ part, const float* __restrict__ gnum,
-                                                          const float* __restrict__ gden, T* __restrict__ dpred) {
-  __shared__ float red[4];
-  float acc = 0.f, npos = 0.f;
-  const float sc = BWD ? gnum[0] / gden[0] : 0.f;
-  const long long total = (long long)a.N * a.R, pix_per_img = a.R / a.A;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long n = i / a.R, r = i - n * a.R, px = r / a.A;
-    const int an = (int)(r - px * a.A);
-    const long long po = (n * pix_per_img + px) * a.pitch + an * 4;
-    const int lab = a.labels[i];
-    const bool pos = lab >= 0 && lab != a.num_classes;
-    f32x4_t gd = {0.f, 0.f, 0.f, 0.f};
-    if (pos) {
-      npos += 1.f;
-      const f32x4_t d = *reinterpret_cast<const f32x4_t*>(a.pred + po), anc = *reinterpret_cast<const f32x4_t*>(a.anchors + r * 4);
-      const f32x4_t gt = *reinterpret_cast<const f32x4_t*>(a.gt + i * 4);
-      const float aw = anc[2] - anc[0], ah = anc[3] - anc[1], acx = anc[0] + 0.5f * aw, acy = anc[1] + 0.5f * ah;
-      const float dw = d[2] / a.ww, dh = d[3] / a.wh;
-      const bool cw_ = dw > a.clampv, ch_ = dh > a.clampv;
-      const float pw = expf(cw_ ? a.clampv : dw) * aw, ph = expf(ch_ ? a.clampv : dh) * ah;
-      const float pcx = d[0] / a.wx * aw + acx, pcy = d[1] / a.wy * ah + acy;
-      const float box[4] = {pcx - 0.5f * pw, pcy - 0.5f * ph, pcx + 0.5f * pw, pcy + 0.5f * ph};
-      const float gb[4] = {gt[0], gt[1], gt[2], gt[3]};
-      float g[4];
-      acc += giou_pair(box, gb, 1e-7f, BWD ? g : nullptr);
-      if (BWD) {
-        gd[0] = (g[0] + g[2]) * aw / a.wx;
-        gd[1] = (g[1] + g[3]) * ah / a.wy;
-        gd[2] = cw_ ? 0.f : (g[2] - g[0]) * 0.5f * pw / a.ww;
-        gd[3] = ch_ ? 0.f : (g[3] - g[1]) * 0.5f * ph / a.wh;
-      }
-    }
-    if (BWD) {
-#pragma unroll
-      for (int e = 0; e < 4; ++e) dpred[po + e] = (T)(gd[e] * sc);
-    }
-  }
-  if (!BWD) {
-    acc = block_sum_256(acc, red);
-    npos = block_sum_256(npos, red);
-    if (threadIdx.x == 0) { part[blockIdx.x] = acc; part[RED + blockIdx.x] = npos; }
-  }
-}
-
-// sums[0] = smooth-L1 sum over positives, sums[1] = number of positives; normalizer <- m*normalizer + (1-m)*max(npos,1)
-__global__ void retina_finish_kernel(const float* __restrict__ part, int nblk_, float* __restrict__ sums, float* __restrict__ normalizer,
-                                     float momentum) {
-  __shared__ float red[4];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < nblk_; i += 256) { a += part[i]; b += part[RED + i]; }
-  a = block_sum_256(a, red);
-  b = block_sum_256(b, red);
-  if (threadIdx.x == 0) {
-    sums[0] = a; sums[1] = b;
-    if (normalizer) normalizer[0] = momentum * normalizer[0] + (1.f - momentum) * fmaxf(b, 1.f);
-  }
-}
-
-inline int nblk(long long n, int cap = RED) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
 }
 
 }  // namespace
@@ -623,7 +443,7 @@ inline int nblk(long long n, int cap = RED) {
 extern "C" int sod_box_iou_rotated(const float* boxes1, int n1, const float* boxes2, int n2, float* iou_out, void* stream) {
   if (n1 < 0 || n2 < 0 || ((long long)n1 * n2 > 0 && (!boxes1 || !boxes2 || !iou_out))) return SOD_EARG;
   if ((long long)n1 * n2 == 0) return SOD_OK;
-  SOD_LAUNCH(pairwise_iou_rotated_kernel, dim3(nblk((long long)n1 * n2, 4096)), dim3(256), 0, (hipStream_t)stream, boxes1, n1, boxes2, n2, iou_out);
+  SOD_LAUNCH(pairwise_iou_rotated_kernel, dim3(sod_nblk((long long)n1 * n2, 4096)), dim3(256), 0, (hipStream_t)stream, boxes1, n1, boxes2, n2, iou_out);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -643,7 +463,7 @@ extern "C" int sod_roi_align_fwd(const void* x, const float* rois, float* out, i
   if (rc) return rc;
   if (R == 0) return SOD_OK;      // nothing to do: rois and out of an empty call may be NULL
   if (!out) return SOD_EARG;
-  SOD_LAUNCH((roi_align_kernel<false, false>), dim3(nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
+  SOD_LAUNCH((roi_align_kernel<false, false>), dim3(sod_nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -655,7 +475,7 @@ extern "C" int sod_roi_align_fwd_f32(const float* x, const float* rois, float* o
   if (rc) return rc;
   if (R == 0) return SOD_OK;      // nothing to do: rois and out of an empty call may be NULL
   if (!out) return SOD_EARG;
-  SOD_LAUNCH((roi_align_kernel<false, true>), dim3(nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
+  SOD_LAUNCH((roi_align_kernel<false, true>), dim3(sod_nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, out, nullptr, nullptr);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -673,7 +493,7 @@ extern "C" int sod_roi_align_bwd(const float* dout, const float* rois, float* dx
     SOD_CHECK_LAUNCH();
     return SOD_OK;
   }
-  SOD_LAUNCH((roi_align_kernel<true, false>), dim3(nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, nullptr, dout, dx);
+  SOD_LAUNCH((roi_align_kernel<true, false>), dim3(sod_nblk((long long)R * PH * PW * (C / 8), 8192)), dim3(256), 0, (hipStream_t)stream, a, nullptr, dout, dx);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -682,9 +502,9 @@ extern "C" int sod_giou_loss_xyxy(const float* boxes1, const float* boxes2, long
                                   const float* grad_scale, float* dboxes1, float* ws, void* stream) {
   if (!boxes1 || !boxes2 || P < 0 || (sum_out && !ws)) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = nblk(P);
+  const int g = sod_nblk(P);
   SOD_LAUNCH(giou_xyxy_kernel, dim3(g), dim3(256), 0, st, boxes1, boxes2, P, eps, elem_out, sum_out ? ws : nullptr, grad_scale, dboxes1);
-  if (sum_out) SOD_LAUNCH(finish_sum2, dim3(1), dim3(256), 0, st, ws, g, sum_out);
+  if (sum_out) SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -693,9 +513,9 @@ extern "C" int sod_smooth_l1_loss(const float* input, const float* target, long 
                                   const float* grad_scale, float* dinput, float* ws, void* stream) {
   if (!input || !target || n < 0 || (sum_out && !ws)) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = nblk(n);
+  const int g = sod_nblk(n);
   SOD_LAUNCH(smooth_l1_kernel, dim3(g), dim3(256), 0, st, input, target, n, beta, elem_out, sum_out ? ws : nullptr, grad_scale, dinput);
-  if (sum_out) SOD_LAUNCH(finish_sum2, dim3(1), dim3(256), 0, st, ws, g, sum_out);
+  if (sum_out) SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -715,7 +535,7 @@ static int anchor_match_impl(const float* gt_boxes, int G, const float* anchors,
   if (!gt_boxes || !gt_best_ws) return SOD_EARG;
   hipError_t e = hipMemsetAsync(gt_best_ws, 0, sizeof(unsigned) * G, st);
   if (e != hipSuccess) return (int)e;
-  const int g = nblk(A, 2048);
+  const int g = sod_nblk(A, 2048);
   if (D == 5) SOD_LAUNCH(anchor_match1_rot_kernel, dim3(g), dim3(256), sizeof(unsigned) * G, st, gt_boxes, G, anchors, A, matched_vals, matches, gt_best_ws);
   else SOD_LAUNCH(anchor_match1_kernel<D>, dim3(g), dim3(256), sizeof(unsigned) * G, st, gt_boxes, G, anchors, A, matched_vals, matches, gt_best_ws);
   SOD_LAUNCH(anchor_match2_kernel<D>, dim3(g), dim3(256), 0, st, gt_boxes, G, anchors, A, matched_vals, gt_best_ws, thr_lo, thr_hi,
@@ -791,83 +611,8 @@ extern "C" int sod_retina_targets(const float* anchors, int A, const float* gt_b
                                   const signed char* match_labels, int num_classes, const float* weights4, int* gt_labels, float* gt_deltas,
                                   void* stream) {
   if (!anchors || A <= 0 || !gt_labels || !gt_deltas || !weights4 || (G > 0 && (!gt_boxes || !gt_classes || !matches || !match_labels))) return SOD_EARG;
-  SOD_LAUNCH(retina_targets_kernel, dim3(nblk(A, 2048)), dim3(256), 0, (hipStream_t)stream, anchors, A, gt_boxes, gt_classes, G, matches, match_labels,
+  SOD_LAUNCH(retina_targets_kernel, dim3(sod_nblk(A, 2048)), dim3(256), 0, (hipStream_t)stream, anchors, A, gt_boxes, gt_classes, G, matches, match_labels,
              num_classes, weights4[0], weights4[1], weights4[2], weights4[3], gt_labels, gt_deltas);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                       int num_classes, float beta, float* sums2, float* normalizer, float momentum, float* ws, void* stream) {
-  if (!pred || !gt_labels || !gt_deltas || !sums2 || !ws || N <= 0 || R <= 0 || A <= 0 || R % A || pitch < A * 4) return SOD_EARG;
-  RetinaBoxArgs a{pred, gt_labels, gt_deltas, N, R, A, pitch, num_classes, beta};
-  hipStream_t st = (hipStream_t)stream;
-  const int g = nblk((long long)N * R);
-  SOD_LAUNCH((retina_box_kernel<false, __bf16>), dim3(g), dim3(256), 0, st, a, ws, nullptr, nullptr, nullptr);
-  SOD_LAUNCH(retina_finish_kernel, dim3(1), dim3(256), 0, st, ws, g, sums2, normalizer, momentum);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-static int retina_giou_fill(RetinaGiouArgs& a, const float* pred, int pitch, const int* labels, const float* anchors, const float* gt, int N, int R,
-                            int A, int K, const float* w4, float clampv) {
-  if (!pred || !labels || !anchors || !gt || !w4 || N <= 0 || R <= 0 || A <= 0 || R % A || pitch < A * 4) return SOD_EARG;
-  for (int i = 0; i < 4; ++i) if (!(w4[i] > 0.f)) return SOD_EARG;
-  a = RetinaGiouArgs{pred, labels, anchors, gt, N, R, A, pitch, K, w4[0], w4[1], w4[2], w4[3], clampv};
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_giou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
-                                        int N, int R, int A, int num_classes, const float* weights4, float scale_clamp, float* sums2,
-                                        float* normalizer, float momentum, float* ws, void* stream) {
-  RetinaGiouArgs a{};
-  int rc = retina_giou_fill(a, pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights4, scale_clamp);
-  if (rc || !sums2 || !ws) return rc ? rc : SOD_EARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = nblk((long long)N * R);
-  SOD_LAUNCH((retina_giou_kernel<false, __bf16>), dim3(g), dim3(256), 0, st, a, ws, nullptr, nullptr, nullptr);
-  SOD_LAUNCH(retina_finish_kernel, dim3(1), dim3(256), 0, st, ws, g, sums2, normalizer, momentum);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_giou_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
-                                        int N, int R, int A, int num_classes, const float* weights4, float scale_clamp,
-                                        const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream) {
-  RetinaGiouArgs a{};
-  int rc = retina_giou_fill(a, pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights4, scale_clamp);
-  if (rc || !grad_num || !grad_den || !dpred_bf16) return rc ? rc : SOD_EARG;
-  SOD_LAUNCH((retina_giou_kernel<true, __bf16>), dim3(nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den,
-             (__bf16*)dpred_bf16);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                       int num_classes, float beta, const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream) {
-  if (!pred || !gt_labels || !gt_deltas || !grad_num || !grad_den || !dpred_bf16 || N <= 0 || R <= 0 || A <= 0 || R % A || pitch < A * 4) return SOD_EARG;
-  RetinaBoxArgs a{pred, gt_labels, gt_deltas, N, R, A, pitch, num_classes, beta};
-  SOD_LAUNCH((retina_box_kernel<true, __bf16>), dim3(nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den, (__bf16*)dpred_bf16);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_giou_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
-                                            int N, int R, int A, int num_classes, const float* weights4, float scale_clamp,
-                                            const float* grad_num, const float* grad_den, float* dpred, void* stream) {
-  RetinaGiouArgs a{};
-  int rc = retina_giou_fill(a, pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights4, scale_clamp);
-  if (rc || !grad_num || !grad_den || !dpred) return rc ? rc : SOD_EARG;
-  SOD_LAUNCH((retina_giou_kernel<true, float>), dim3(nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den, dpred);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                           int num_classes, float beta, const float* grad_num, const float* grad_den, float* dpred, void* stream) {
-  if (!pred || !gt_labels || !gt_deltas || !grad_num || !grad_den || !dpred || N <= 0 || R <= 0 || A <= 0 || R % A || pitch < A * 4) return SOD_EARG;
-  RetinaBoxArgs a{pred, gt_labels, gt_deltas, N, R, A, pitch, num_classes, beta};
-  SOD_LAUNCH((retina_box_kernel<true, float>), dim3(nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den, dpred);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }

@@ -13,15 +13,6 @@
 
 namespace {
 
-constexpr int RPD_RED = 1024;
-
-inline int rpd_nblk(long long n, int cap = RPD_RED) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ------------------------------------------------------------------------------------------------ Scale (layers/scale.py:5-11)
 __global__ __launch_bounds__(256) void rpd_scale_fwd_kernel(const float* __restrict__ x, const float* __restrict__ scale, float* __restrict__ y,
                                                             long long n) {
@@ -42,15 +33,6 @@ __global__ __launch_bounds__(256) void rpd_scale_bwd_kernel(const float* __restr
   }
   acc = block_sum_256(acc, red);
   if (threadIdx.x == 0) part[blockIdx.x] = acc;
-}
-
-// block partials added in index order: the same bits from run to run
-__global__ void rpd_finish_kernel(const float* __restrict__ part, int nb, float* __restrict__ out, int accumulate) {
-  __shared__ float red[4];
-  float v = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) v += part[i];
-  v = block_sum_256(v, red);
-  if (threadIdx.x == 0) out[0] = accumulate ? out[0] + v : v;
 }
 
 // ------------------------------------------------------------------------------------------------ points -> LTRB (:709-745, :222-234)
@@ -239,7 +221,7 @@ __global__ void rpd_finalize_kernel(const float* __restrict__ focal_sum, const f
 extern "C" int sod_level_scale_fwd(const float* x, const float* scale, float* y, long long n, void* stream) {
   if (!x || !scale || !y || n < 0) return SOD_EARG;
   if (n == 0) return SOD_OK;
-  SOD_LAUNCH(rpd_scale_fwd_kernel, dim3(rpd_nblk(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, scale, y, n);
+  SOD_LAUNCH(rpd_scale_fwd_kernel, dim3(sod_nblk(n, 8192)), dim3(256), 0, (hipStream_t)stream, x, scale, y, n);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -249,9 +231,9 @@ extern "C" int sod_level_scale_bwd(const float* dy, const float* x, const float*
   if (!dy || !x || !scale || !dx || !dscale || !ws || n < 0) return SOD_EARG;
   if (n == 0) return SOD_OK;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rpd_nblk(n);
+  const int g = sod_nblk(n);
   SOD_LAUNCH(rpd_scale_bwd_kernel, dim3(g), dim3(256), 0, st, dy, x, scale, dx, n, ws);
-  SOD_LAUNCH(rpd_finish_kernel, dim3(1), dim3(256), 0, st, ws, g, dscale, 1);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, dscale, 1);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -274,7 +256,7 @@ extern "C" int sod_points2ltrb_fwd(const float* pts, const float* add, int ld, i
   int rc = p2l_fill(a, ld, N, H, W, loc_stride, point_stride, num_points, out_img_stride, arg_img_stride);
   if (rc) return rc;
   a.pts = pts; a.add = add; a.ltrb = ltrb; a.boxes = boxes; a.arg = argidx;
-  SOD_LAUNCH(p2l_fwd_kernel, dim3(rpd_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a);
+  SOD_LAUNCH(p2l_fwd_kernel, dim3(sod_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -286,7 +268,7 @@ extern "C" int sod_points2ltrb_bwd(const float* dltrb, long long out_img_stride,
   int rc = p2l_fill(a, ld, N, H, W, 0, point_stride, num_points, out_img_stride, arg_img_stride);
   if (rc) return rc;
   a.arg = const_cast<unsigned*>(argidx);
-  SOD_LAUNCH(p2l_bwd_kernel, dim3(rpd_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, dltrb, dpts_f32, (__bf16*)dpts_bf16);
+  SOD_LAUNCH(p2l_bwd_kernel, dim3(sod_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, dltrb, dpts_f32, (__bf16*)dpts_bf16);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -323,7 +305,7 @@ extern "C" int sod_fcos_rpd_refine_targets(const float* gt_boxes, const int* gt_
     hipError_t e = hipMemsetAsync(gt_best_ws, 0, sizeof(unsigned) * total_gt, st);
     if (e != hipSuccess) return (int)e;
   }
-  const int gx = rpd_nblk(a.L, 2048);
+  const int gx = sod_nblk(a.L, 2048);
   SOD_LAUNCH(rt_match1_kernel, dim3(gx, N), dim3(256), sizeof(unsigned) * (max_gt > 0 ? max_gt : 1), st, a);
   SOD_LAUNCH(rt_match2_kernel, dim3(gx, N), dim3(256), 0, st, a);
   SOD_CHECK_LAUNCH();

@@ -13,21 +13,6 @@
 
 namespace {
 
-constexpr int RED_BLOCKS = 1024;   // max partials per reduction (workspace floats per reduced scalar)
-
-__global__ void finish_sum_kernel(const float* __restrict__ part, int nblk, int nscalars, float* __restrict__ out,
-                                  int accumulate) {
-  // one wave per scalar; sums partials in a fixed order
-  __shared__ float red[4];
-  for (int s = 0; s < nscalars; ++s) {
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) v += part[s * RED_BLOCKS + i];
-    v = block_sum_256(v, red);
-    if (threadIdx.x == 0) out[s] = accumulate ? out[s] + v : v;
-    __syncthreads();
-  }
-}
-
 // sigmoid(x) and softplus(-|x|) = log1p(exp(-|x|)) from ONE hardware exponential (v_exp_f32) and, only where it is needed, one
 // hardware logarithm: for e = exp(-|x|) < 2^-5 the alternating series e - e^2/2 + e^3/3 - e^4/4 is exact to < 1e-8 relative, above that
 // 1 + e keeps >= 19 significant bits and v_log_f32 is accurate to ~1 ulp.  (The libm expf / log1pf / division sequences made these
@@ -389,7 +374,7 @@ __global__ __launch_bounds__(256) void fcos_assign_kernel(const AssignArgs a, fl
   if (threadIdx.x == 0) {
     const int b = blockIdx.y * gridDim.x + blockIdx.x;
     part[b] = npos;
-    part[(WITH_INDEX ? 2 : 1) * RED_BLOCKS + b] = sctr;      // <true>: slot 1 belongs to the selection pass (stats3 order)
+    part[(WITH_INDEX ? 2 : 1) * SOD_RED + b] = sctr;      // <true>: slot 1 belongs to the selection pass (stats3 order)
   }
 }
 
@@ -470,16 +455,16 @@ __global__ __launch_bounds__(256) void fcos_topk_select_kernel(const AssignArgs 
       }
     }
   }
-  if (lane == 0) part[RED_BLOCKS + wave] = ssel;
+  if (lane == 0) part[SOD_RED + wave] = ssel;
 }
 
-// stats3 = {sum part[0..n0), sum part[RED_BLOCKS..+n1), sum part[2 RED_BLOCKS..+n2)}: fixed order, as finish_sum_kernel
+// stats3 = {sum part[0..n0), sum part[SOD_RED..+n1), sum part[2 SOD_RED..+n2)}: fixed order, as sod_finish_sums_kernel
 __global__ void finish_sum3_kernel(const float* __restrict__ part, int n0, int n1, int n2, float* __restrict__ out) {
   __shared__ float red[4];
   for (int s = 0; s < 3; ++s) {
     const int nblk = s == 0 ? n0 : (s == 1 ? n1 : n2);
     float v = 0.f;
-    for (int i = threadIdx.x; i < nblk; i += 256) v += part[s * RED_BLOCKS + i];
+    for (int i = threadIdx.x; i < nblk; i += 256) v += part[s * SOD_RED + i];
     v = block_sum_256(v, red);
     if (threadIdx.x == 0) out[s] = v;
     __syncthreads();
@@ -530,7 +515,7 @@ __global__ __launch_bounds__(256) void regctr_fwd_kernel(const RegCtrArgs a, flo
   }
   lreg = block_sum_256(lreg, red);
   lctr = block_sum_256(lctr, red);
-  if (threadIdx.x == 0) { part[blockIdx.x] = lreg; part[RED_BLOCKS + blockIdx.x] = lctr; }
+  if (threadIdx.x == 0) { part[blockIdx.x] = lreg; part[SOD_RED + blockIdx.x] = lctr; }
 }
 
 // writes d(box_raw) and d(ctr_logit) as bf16 into a padded [M, ld_out] buffer (columns 0..3 box, ctr_col ctr,
@@ -595,7 +580,7 @@ __global__ __launch_bounds__(256) void regctr_bwd_kernel(const RegCtrArgs a, con
 #pragma unroll
   for (int l = 0; l < SOD_MAX_LEVELS; ++l) {
     const float v = block_sum_256(dsc[l], red);
-    if (threadIdx.x == 0) part[l * RED_BLOCKS + blockIdx.x] = v;
+    if (threadIdx.x == 0) part[l * SOD_RED + blockIdx.x] = v;
   }
 }
 
@@ -611,16 +596,9 @@ __global__ void fcos_finalize_kernel(const float* __restrict__ focal_sum, const 
   }
 }
 
-inline int grid_for(long long n) {
-  long long g = (n + 255) / 256;
-  if (g > RED_BLOCKS) g = RED_BLOCKS;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 }  // namespace
 
-extern "C" long long sod_reduce_workspace_bytes(void) { return (long long)RED_BLOCKS * 8 * sizeof(float); }
+extern "C" long long sod_reduce_workspace_bytes(void) { return (long long)SOD_RED * 8 * sizeof(float); }
 
 extern "C" int sod_sigmoid_focal_loss_fwd(const float* logits, const int* labels, const float* dense_targets,
                                           long long M, int K, int ld, float alpha, float gamma, float* elem_out,
@@ -629,13 +607,13 @@ extern "C" int sod_sigmoid_focal_loss_fwd(const float* logits, const int* labels
   hipStream_t st = (hipStream_t)stream;
   const bool vec = labels && !dense_targets && (K & 3) == 0 && (ld & 3) == 0 && M * (long long)K < (1ll << 31) &&
                    ((uintptr_t)logits & 15) == 0 && ((uintptr_t)elem_out & 15) == 0;
-  const int g = vec ? grid_for(M * K / 4) : grid_for(M * K);
+  const int g = vec ? sod_nblk(M * K / 4) : sod_nblk(M * K);
   if (vec)
     SOD_LAUNCH(focal_fwd_vec4_kernel, dim3(g), dim3(256), 0, st, logits, labels, (uint32_t)(M * K / 4), make_fastdiv((uint32_t)(K / 4)), ld, alpha,
                gamma, elem_out, K, ws);
   else
     SOD_LAUNCH(focal_fwd_kernel, dim3(g), dim3(256), 0, st, logits, labels, dense_targets, M, K, ld, alpha, gamma, elem_out, ws);
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -647,10 +625,10 @@ extern "C" int sod_sigmoid_focal_loss_fwd_grad(const float* logits, const int* l
     return SOD_EARG;      // the vectorised form only (class-index labels, 4 classes per lane): callers fall back to the two-pass entry points
   hipStream_t st = (hipStream_t)stream;
   const uint32_t total4 = (uint32_t)(M * ld_out / 4);
-  const int g = grid_for(M * ld_out / 4);
+  const int g = sod_nblk(M * ld_out / 4);
   SOD_LAUNCH(focal_fwd_grad_vec4_kernel, dim3(g), dim3(256), 0, st, logits, labels, total4, make_fastdiv((uint32_t)(ld_out / 4)), K, ld, alpha, gamma,
              ws, (__bf16*)dlogits_bf16, ld_out);
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -665,7 +643,7 @@ extern "C" int sod_sigmoid_focal_loss_bwd(const float* logits, const int* labels
                    ((uintptr_t)logits & 15) == 0 && ((uintptr_t)dlogits & 15) == 0;
   if (vec) {
     const uint32_t total4 = (uint32_t)(M * ld_out / 4);
-    const int gv = grid_for(M * ld_out / 4) * 2;
+    const int gv = sod_nblk(M * ld_out / 4) * 2;
     const FastDiv d = make_fastdiv((uint32_t)(ld_out / 4));
     if (out_bf16)
       SOD_LAUNCH(focal_bwd_vec4_kernel<true>, dim3(gv), dim3(256), 0, st, logits, labels, total4, d, K, ld, alpha, gamma, scale_num, scale_den, den_mul, den_min, dlogits, ld_out);
@@ -674,7 +652,7 @@ extern "C" int sod_sigmoid_focal_loss_bwd(const float* logits, const int* labels
     SOD_CHECK_LAUNCH();
     return SOD_OK;
   }
-  const int g = grid_for(M * ld_out) * 2;
+  const int g = sod_nblk(M * ld_out) * 2;
   if (out_bf16)
     SOD_LAUNCH(focal_bwd_kernel<true>, dim3(g), dim3(256), 0, st, logits, labels, dense_targets, M, K, ld, alpha, gamma, scale_num, scale_den, den_mul, den_min, dlogits, ld_out);
   else
@@ -687,9 +665,9 @@ extern "C" int sod_iou_loss_fwd(const float* pred, const float* target, const fl
                                 long long P, int loss_type, float* elem_out, float* sum_out, float* ws, void* stream) {
   if (!pred || !target || !sum_out || !ws || P < 0 || loss_type < 0 || loss_type > 2) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = grid_for(P);
+  const int g = sod_nblk(P);
   SOD_LAUNCH(iou_fwd_kernel, dim3(g), dim3(256), 0, st, pred, target, weight, mask, mask_bg, P, loss_type, elem_out, ws);
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -697,7 +675,7 @@ extern "C" int sod_iou_loss_fwd(const float* pred, const float* target, const fl
 extern "C" int sod_iou_loss_bwd(const float* pred, const float* target, const float* weight, const int* mask, int mask_bg,
                                 long long P, int loss_type, const float* grad_scale, float* dpred, void* stream) {
   if (!pred || !target || !dpred || P < 0 || loss_type < 0 || loss_type > 2) return SOD_EARG;
-  SOD_LAUNCH(iou_bwd_kernel, dim3(grid_for(P)), dim3(256), 0, (hipStream_t)stream, pred, target, weight, mask, mask_bg, P, loss_type, grad_scale, dpred);
+  SOD_LAUNCH(iou_bwd_kernel, dim3(sod_nblk(P)), dim3(256), 0, (hipStream_t)stream, pred, target, weight, mask, mask_bg, P, loss_type, grad_scale, dpred);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -719,7 +697,7 @@ static int fill_assign(AssignArgs& a, const float* boxes, const int* classes, co
   for (int l = nlevels; l <= SOD_MAX_LEVELS; ++l) a.lvl_off[l] = off;
   a.L = off; a.labels = labels; a.reg = reg_targets; a.ctr = ctr_targets;
   gx = (a.L + 255) / 256;
-  if (gx * N > RED_BLOCKS) gx = RED_BLOCKS / N;
+  if (gx * N > SOD_RED) gx = SOD_RED / N;
   if (gx < 1) return SOD_EARG;
   return SOD_OK;
 }
@@ -736,7 +714,7 @@ extern "C" int sod_fcos_assign(const float* boxes, const int* classes, const int
   if (rc) return rc;
   hipStream_t st = (hipStream_t)stream;
   SOD_LAUNCH(fcos_assign_kernel<false>, dim3(gx, N), dim3(256), 0, st, a, ws);
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, gx * N, 2, stats, 0);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, gx * N, 2, stats, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -802,12 +780,12 @@ static int regctr_fwd_impl(int use_sel, const unsigned char* sel, SOD_REGCTR_PAR
   a.reg_t = reg_targets; a.ctr_t = ctr_targets; a.scales = scales; a.M = N * a.L; a.num_classes = num_classes;
   a.type = loss_type; a.norm_reg = norm_reg_targets; a.sel = sel;
   hipStream_t st = (hipStream_t)stream;
-  const int g = grid_for(a.M);
+  const int g = sod_nblk(a.M);
   if (use_sel)
     SOD_LAUNCH(regctr_fwd_kernel<true>, dim3(g), dim3(256), 0, st, a, ws);
   else
     SOD_LAUNCH(regctr_fwd_kernel<false>, dim3(g), dim3(256), 0, st, a, ws);
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, 2, sums, 0);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 2, sums, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -830,7 +808,7 @@ static int regctr_bwd_impl(int out_f32, int use_sel, const unsigned char* sel, S
   a.reg_t = reg_targets; a.ctr_t = ctr_targets; a.scales = scales; a.M = N * a.L; a.num_classes = num_classes;
   a.type = loss_type; a.norm_reg = norm_reg_targets; a.sel = sel;
   hipStream_t st = (hipStream_t)stream;
-  const int g = grid_for(a.M);
+  const int g = sod_nblk(a.M);
   if (out_f32) {
     if (use_sel) launch_regctr_bwd<float, true>(a, g, st, SOD_REGCTR_BWD_ARGS);
     else launch_regctr_bwd<float, false>(a, g, st, SOD_REGCTR_BWD_ARGS);
@@ -838,7 +816,7 @@ static int regctr_bwd_impl(int out_f32, int use_sel, const unsigned char* sel, S
     if (use_sel) launch_regctr_bwd<__bf16, true>(a, g, st, SOD_REGCTR_BWD_ARGS);
     else launch_regctr_bwd<__bf16, false>(a, g, st, SOD_REGCTR_BWD_ARGS);
   }
-  SOD_LAUNCH(finish_sum_kernel, dim3(1), dim3(256), 0, st, ws, g, nlevels, dscales, 1);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, nlevels, dscales, 1);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }

@@ -10,28 +10,7 @@
 
 namespace {
 
-constexpr int RC_RED = 1024;
-constexpr float RC_PI = 3.14159265358979323846f;
-
-inline int rc_nblk(long long n, int cap = RC_RED) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-__global__ void rc_finish(const float* __restrict__ part, int nb, int nsum, float* __restrict__ out) {
-  __shared__ float red[4];
-  for (int s = 0; s < nsum; ++s) {
-    float v = 0.f;
-    for (int i = threadIdx.x; i < nb; i += 256) v += part[s * RC_RED + i];
-    v = block_sum_256(v, red);
-    if (threadIdx.x == 0) out[s] = v;
-    __syncthreads();
-  }
-}
-
-struct W5 { float w[5]; };
+#include "box_transform.h"
 
 // d2 Box2BoxTransform.get_deltas (XYXY) / Box2BoxTransformRotated.get_deltas (cx, cy, w, h, angle in degrees)
 __global__ __launch_bounds__(256) void get_deltas_kernel(const float* __restrict__ src, const float* __restrict__ tgt, long long n, int D, W5 w,
@@ -40,20 +19,8 @@ __global__ __launch_bounds__(256) void get_deltas_kernel(const float* __restrict
     const float* s = src + i * D;
     const float* t = tgt + i * D;
     float* o = out + i * D;
-    if (D == 4) {
-      const float sw = s[2] - s[0], sh = s[3] - s[1], scx = s[0] + 0.5f * sw, scy = s[1] + 0.5f * sh;
-      const float tw = t[2] - t[0], th = t[3] - t[1], tcx = t[0] + 0.5f * tw, tcy = t[1] + 0.5f * th;
-      o[0] = w.w[0] * (tcx - scx) / sw; o[1] = w.w[1] * (tcy - scy) / sh;
-      o[2] = w.w[2] * logf(tw / sw); o[3] = w.w[3] * logf(th / sh);
-    } else {
-      o[0] = w.w[0] * (t[0] - s[0]) / s[2]; o[1] = w.w[1] * (t[1] - s[1]) / s[3];
-      o[2] = w.w[2] * logf(t[2] / s[2]); o[3] = w.w[3] * logf(t[3] / s[3]);
-      float da = t[4] - s[4];
-      da = fmodf(da + 180.f, 360.f);
-      if (da < 0.f) da += 360.f;            // python's % (result takes the sign of the divisor)
-      da -= 180.f;
-      o[4] = da * w.w[4] * RC_PI / 180.f;
-    }
+    if (D == 4) xyxy_get_deltas(s, t, w.w, o);
+    else rot_get_deltas(s, t, w.w, o);
   }
 }
 
@@ -67,21 +34,8 @@ __global__ __launch_bounds__(256) void apply_deltas_kernel(const float* __restri
     const float* b = boxes + r * D;
     const float* d = deltas + r * ld + c * D;
     float* o = out + (r * k + c) * D;
-    if (D == 4) {
-      const float bw = b[2] - b[0], bh = b[3] - b[1], cx = b[0] + 0.5f * bw, cy = b[1] + 0.5f * bh;
-      const float dx = d[0] / w.w[0], dy = d[1] / w.w[1], dw = fminf(d[2] / w.w[2], clampv), dh = fminf(d[3] / w.w[3], clampv);
-      const float pcx = dx * bw + cx, pcy = dy * bh + cy, pw = expf(dw) * bw, ph = expf(dh) * bh;
-      o[0] = pcx - 0.5f * pw; o[1] = pcy - 0.5f * ph; o[2] = pcx + 0.5f * pw; o[3] = pcy + 0.5f * ph;
-    } else {
-      const float dx = d[0] / w.w[0], dy = d[1] / w.w[1], dw = fminf(d[2] / w.w[2], clampv), dh = fminf(d[3] / w.w[3], clampv);
-      const float da = d[4] / w.w[4];
-      o[0] = dx * b[2] + b[0]; o[1] = dy * b[3] + b[1];
-      o[2] = expf(dw) * b[2]; o[3] = expf(dh) * b[3];
-      float a = da * 180.f / RC_PI + b[4];
-      a = fmodf(a + 180.f, 360.f);
-      if (a < 0.f) a += 360.f;
-      o[4] = a - 180.f;
-    }
+    if (D == 4) xyxy_apply_deltas<CLAMP_DROPS_NAN>(d, b, w.w, clampv, o);
+    else rot_apply_deltas(d, b, w.w, clampv, o);
   }
 }
 
@@ -232,11 +186,7 @@ __global__ __launch_bounds__(256) void frcnn_box_kernel(const float* __restrict_
   }
 }
 
-inline bool fill_w(W5& w, const float* weights, int D) {
-  if (!weights || (D != 4 && D != 5)) return false;
-  for (int i = 0; i < D; ++i) { w.w[i] = weights[i]; if (!(w.w[i] > 0.f)) return false; }
-  return true;
-}
+inline bool fill_w(W5& w, const float* weights, int D) { return (D == 4 || D == 5) && fill_w5(w, weights, D); }
 
 }  // namespace
 
@@ -428,7 +378,7 @@ extern "C" int sod_box2box_get_deltas(const float* src, const float* tgt, long l
   W5 w{};
   if (!src || !tgt || !deltas || n < 0 || !fill_w(w, weights, box_dim)) return SOD_EARG;
   if (n == 0) return SOD_OK;
-  SOD_LAUNCH(get_deltas_kernel, dim3(rc_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, src, tgt, n, box_dim, w, deltas);
+  SOD_LAUNCH(get_deltas_kernel, dim3(sod_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, src, tgt, n, box_dim, w, deltas);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -440,7 +390,7 @@ extern "C" int sod_box2box_apply_deltas(const float* deltas, const float* boxes,
   if (ld <= 0) ld = k * box_dim;
   if (ld < k * box_dim) return SOD_EARG;
   if (n == 0) return SOD_OK;
-  SOD_LAUNCH(apply_deltas_kernel, dim3(rc_nblk(n * k, 4096)), dim3(256), 0, (hipStream_t)stream, deltas, boxes, n, k, box_dim, ld, w, scale_clamp, out);
+  SOD_LAUNCH(apply_deltas_kernel, dim3(sod_nblk(n * k, 4096)), dim3(256), 0, (hipStream_t)stream, deltas, boxes, n, k, box_dim, ld, w, scale_clamp, out);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -448,9 +398,9 @@ extern "C" int sod_box2box_apply_deltas(const float* deltas, const float* boxes,
 extern "C" int sod_bce_logits_loss_fwd(const float* logits, const signed char* labels, long long n, float* sum_out, float* ws, void* stream) {
   if (!logits || !labels || !sum_out || !ws || n < 0) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rc_nblk(n);
+  const int g = sod_nblk(n);
   SOD_LAUNCH(bce_kernel<false>, dim3(g), dim3(256), 0, st, logits, labels, n, ws, nullptr, 0.f, nullptr);
-  SOD_LAUNCH(rc_finish, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -458,7 +408,7 @@ extern "C" int sod_bce_logits_loss_fwd(const float* logits, const signed char* l
 extern "C" int sod_bce_logits_loss_bwd(const float* logits, const signed char* labels, long long n, const float* grad_scale, float scale_mul,
                                        float* dlogits, void* stream) {
   if (!logits || !labels || !grad_scale || !dlogits || n < 0) return SOD_EARG;
-  SOD_LAUNCH(bce_kernel<true>, dim3(rc_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, logits, labels, n, nullptr, grad_scale, scale_mul, dlogits);
+  SOD_LAUNCH(bce_kernel<true>, dim3(sod_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, logits, labels, n, nullptr, grad_scale, scale_mul, dlogits);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -467,9 +417,9 @@ extern "C" int sod_bce_logits_soft_fwd(const float* logits, const float* targets
                                        float* ws, void* stream) {
   if (!logits || !targets || !labels || !sum_out || !ws || n < 0) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rc_nblk(n);
+  const int g = sod_nblk(n);
   SOD_LAUNCH(bce_soft_kernel<false>, dim3(g), dim3(256), 0, st, logits, targets, labels, bg_label, n, ws, nullptr, 0.f, nullptr);
-  SOD_LAUNCH(rc_finish, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -477,7 +427,7 @@ extern "C" int sod_bce_logits_soft_fwd(const float* logits, const float* targets
 extern "C" int sod_bce_logits_soft_bwd(const float* logits, const float* targets, const int* labels, int bg_label, long long n,
                                        const float* grad_scale, float scale_mul, float* dlogits, void* stream) {
   if (!logits || !targets || !labels || !grad_scale || !dlogits || n < 0) return SOD_EARG;
-  SOD_LAUNCH(bce_soft_kernel<true>, dim3(rc_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, logits, targets, labels, bg_label, n, nullptr,
+  SOD_LAUNCH(bce_soft_kernel<true>, dim3(sod_nblk(n, 4096)), dim3(256), 0, (hipStream_t)stream, logits, targets, labels, bg_label, n, nullptr,
              grad_scale, scale_mul, dlogits);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -487,9 +437,9 @@ extern "C" int sod_rpn_loc_loss_fwd(const float* pred, const float* target, cons
                                     float* sum_out, float* ws, void* stream) {
   if (!pred || !target || !labels || !sum_out || !ws || n < 0 || box_dim <= 0) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rc_nblk(n * box_dim);
+  const int g = sod_nblk(n * box_dim);
   SOD_LAUNCH(loc_kernel<false>, dim3(g), dim3(256), 0, st, pred, target, labels, n, box_dim, beta, ws, nullptr, 0.f, nullptr);
-  SOD_LAUNCH(rc_finish, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -497,7 +447,7 @@ extern "C" int sod_rpn_loc_loss_fwd(const float* pred, const float* target, cons
 extern "C" int sod_rpn_loc_loss_bwd(const float* pred, const float* target, const signed char* labels, long long n, int box_dim, float beta,
                                     const float* grad_scale, float scale_mul, float* dpred, void* stream) {
   if (!pred || !target || !labels || !grad_scale || !dpred || n < 0 || box_dim <= 0) return SOD_EARG;
-  SOD_LAUNCH(loc_kernel<true>, dim3(rc_nblk(n * box_dim, 4096)), dim3(256), 0, (hipStream_t)stream, pred, target, labels, n, box_dim, beta, nullptr,
+  SOD_LAUNCH(loc_kernel<true>, dim3(sod_nblk(n * box_dim, 4096)), dim3(256), 0, (hipStream_t)stream, pred, target, labels, n, box_dim, beta, nullptr,
              grad_scale, scale_mul, dpred);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -506,9 +456,9 @@ extern "C" int sod_rpn_loc_loss_bwd(const float* pred, const float* target, cons
 extern "C" int sod_softmax_ce_fwd(const float* scores, const int* labels, int R, int C, int ld, float* sum_out, float* ws, void* stream) {
   if (!scores || !labels || !sum_out || !ws || R < 0 || C <= 0 || ld < C) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rc_nblk((long long)R * 64);
+  const int g = sod_nblk((long long)R * 64);
   SOD_LAUNCH(ce_kernel<false>, dim3(g), dim3(256), 0, st, scores, labels, R, C, ld, ws, nullptr, 0.f, nullptr);
-  SOD_LAUNCH(rc_finish, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -517,7 +467,7 @@ extern "C" int sod_softmax_ce_bwd(const float* scores, const int* labels, int R,
                                   float* dscores, void* stream) {
   if (!scores || !labels || !grad_scale || !dscores || R < 0 || C <= 0 || ld < C) return SOD_EARG;
   if (R == 0) return SOD_OK;
-  SOD_LAUNCH(ce_kernel<true>, dim3(rc_nblk((long long)R * 64, 4096)), dim3(256), 0, (hipStream_t)stream, scores, labels, R, C, ld, nullptr, grad_scale,
+  SOD_LAUNCH(ce_kernel<true>, dim3(sod_nblk((long long)R * 64, 4096)), dim3(256), 0, (hipStream_t)stream, scores, labels, R, C, ld, nullptr, grad_scale,
              scale_mul, dscores);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -527,9 +477,9 @@ extern "C" int sod_fastrcnn_box_loss_fwd(const float* pred, const int* gt_classe
                                          float beta, float* sum_out, float* ws, void* stream) {
   if (!pred || !gt_classes || !gt_deltas || !sum_out || !ws || R < 0 || K <= 0 || box_dim <= 0 || ld < K * box_dim) return SOD_EARG;
   hipStream_t st = (hipStream_t)stream;
-  const int g = rc_nblk((long long)R * box_dim);
+  const int g = sod_nblk((long long)R * box_dim);
   SOD_LAUNCH(frcnn_box_kernel<false>, dim3(g), dim3(256), 0, st, pred, gt_classes, gt_deltas, R, K, box_dim, ld, beta, ws, nullptr, 0.f, nullptr);
-  SOD_LAUNCH(rc_finish, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -538,7 +488,7 @@ extern "C" int sod_fastrcnn_box_loss_bwd(const float* pred, const int* gt_classe
                                          float beta, const float* grad_scale, float scale_mul, float* dpred, void* stream) {
   if (!pred || !gt_classes || !gt_deltas || !grad_scale || !dpred || R < 0 || K <= 0 || box_dim <= 0 || ld < K * box_dim) return SOD_EARG;
   if (R == 0) return SOD_OK;
-  SOD_LAUNCH(frcnn_box_kernel<true>, dim3(rc_nblk((long long)R * ld, 4096)), dim3(256), 0, (hipStream_t)stream, pred, gt_classes, gt_deltas, R, K,
+  SOD_LAUNCH(frcnn_box_kernel<true>, dim3(sod_nblk((long long)R * ld, 4096)), dim3(256), 0, (hipStream_t)stream, pred, gt_classes, gt_deltas, R, K,
              box_dim, ld, beta, nullptr, grad_scale, scale_mul, dpred);
   SOD_CHECK_LAUNCH();
   return SOD_OK;

@@ -12,15 +12,6 @@
 
 namespace {
 
-constexpr int RP_RED = 1024;
-
-inline int rp_nblk(long long n, int cap = RP_RED) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
 // ------------------------------------------------------------------------------------------------ dcn offsets
 // out[r, 2k] = scale * in[r, 2k+1] - by[k] ; out[r, 2k+1] = scale * in[r, 2k] - bx[k]   (by = k / ks - pad, bx = k % ks - pad)
 // Forward: scale 1, subtract_base 1.  Backward is the same permutation with scale = gradient_mul and no base.
@@ -409,17 +400,8 @@ __global__ __launch_bounds__(256) void rp_box_loss_kernel(const RpBoxArgs a, flo
   if (!BWD) {
     acc = block_sum_256(acc, red);
     cnt = block_sum_256(cnt, red);
-    if (threadIdx.x == 0) { part[blockIdx.x] = acc; part[RP_RED + blockIdx.x] = cnt; }
+    if (threadIdx.x == 0) { part[blockIdx.x] = acc; part[SOD_RED + blockIdx.x] = cnt; }
   }
-}
-
-__global__ void rp_box_finish_kernel(const float* __restrict__ part, int nb, float* __restrict__ sums) {
-  __shared__ float red[4];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < nb; i += 256) { a += part[i]; b += part[RP_RED + i]; }
-  a = block_sum_256(a, red);
-  b = block_sum_256(b, red);
-  if (threadIdx.x == 0) { sums[0] = a; sums[1] = b; }
 }
 
 __global__ void rp_finalize_kernel(const float* __restrict__ focal_sum, const float* __restrict__ init2, const float* __restrict__ refine2,
@@ -443,7 +425,7 @@ extern "C" int sod_reppoints_dcn_offset(const float* pts, float* out, long long 
   while (ks * ks < num_points) ++ks;
   if (ks * ks != num_points || !(ks & 1)) return SOD_EARG;
   if (rows == 0) return SOD_OK;
-  SOD_LAUNCH(rp_dcn_offset_kernel, dim3(rp_nblk(rows * ld, 8192)), dim3(256), 0, (hipStream_t)stream, pts, out, rows, ld, num_points, ks, scale,
+  SOD_LAUNCH(rp_dcn_offset_kernel, dim3(sod_nblk(rows * ld, 8192)), dim3(256), 0, (hipStream_t)stream, pts, out, rows, ld, num_points, ks, scale,
              subtract_base, flip_xy);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -467,7 +449,7 @@ extern "C" int sod_points2bbox_fwd(const float* pts, const float* add, int ld, i
   int rc = p2b_fill(a, ld, N, H, W, grid_stride, point_stride, num_points, box_img_stride, arg_img_stride);
   if (rc) return rc;
   a.pts = pts; a.add = add; a.boxes = boxes; a.arg = argidx;
-  SOD_LAUNCH(p2b_fwd_kernel, dim3(rp_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a);
+  SOD_LAUNCH(p2b_fwd_kernel, dim3(sod_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -479,7 +461,7 @@ extern "C" int sod_points2bbox_bwd(const float* dboxes, long long box_img_stride
   int rc = p2b_fill(a, ld, N, H, W, 0.f, point_stride, num_points, box_img_stride, arg_img_stride);
   if (rc) return rc;
   a.arg = const_cast<unsigned*>(argidx);
-  SOD_LAUNCH(p2b_bwd_kernel, dim3(rp_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, dboxes, dpts_f32, (__bf16*)dpts_bf16);
+  SOD_LAUNCH(p2b_bwd_kernel, dim3(sod_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, dboxes, dpts_f32, (__bf16*)dpts_bf16);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -491,7 +473,7 @@ extern "C" int sod_points2bbox_moment_fwd(const float* pts, const float* add, in
   int rc = p2b_fill(a, ld, N, H, W, grid_stride, point_stride, num_points, box_img_stride, 0);
   if (rc) return rc;
   a.pts = pts; a.add = add; a.boxes = boxes; a.arg = nullptr;
-  SOD_LAUNCH(p2b_moment_fwd_kernel, dim3(rp_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, moment_transfer);
+  SOD_LAUNCH(p2b_moment_fwd_kernel, dim3(sod_nblk((long long)N * H * W, 8192)), dim3(256), 0, (hipStream_t)stream, a, moment_transfer);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -504,7 +486,7 @@ extern "C" int sod_points2bbox_moment_bwd(const float* dboxes, long long box_img
   int rc = p2b_fill(a, ld, N, H, W, grid_stride, point_stride, num_points, box_img_stride, 0);
   if (rc) return rc;
   a.pts = pts; a.add = add;
-  SOD_LAUNCH(p2b_moment_bwd_kernel, dim3(rp_nblk((long long)N * H * W, 1024)), dim3(256), 0, (hipStream_t)stream, a, dboxes, moment_transfer,
+  SOD_LAUNCH(p2b_moment_bwd_kernel, dim3(sod_nblk((long long)N * H * W, 1024)), dim3(256), 0, (hipStream_t)stream, a, dboxes, moment_transfer,
              moment_mul, dpts_f32, (__bf16*)dpts_bf16, dmoment2);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -525,7 +507,7 @@ extern "C" int sod_reppoints_labels(const int* matches, const signed char* match
                                     const int* box_offsets, const float* centers, const float* image_hw, int N, int X, int num_classes,
                                     int* cls_labels, float* refine_boxes, int* objectness, void* stream) {
   if (!matches || !match_labels || !box_offsets || !centers || !image_hw || !cls_labels || !refine_boxes || N <= 0 || X <= 0) return SOD_EARG;
-  SOD_LAUNCH(rp_labels_kernel, dim3(rp_nblk((long long)N * X, 4096)), dim3(256), 0, (hipStream_t)stream, matches, match_labels, gt_boxes, gt_classes,
+  SOD_LAUNCH(rp_labels_kernel, dim3(sod_nblk((long long)N * X, 4096)), dim3(256), 0, (hipStream_t)stream, matches, match_labels, gt_boxes, gt_classes,
              box_offsets, centers, image_hw, N, X, num_classes, cls_labels, refine_boxes, objectness);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
@@ -536,9 +518,9 @@ extern "C" int sod_reppoints_box_loss_fwd(const float* pred, const float* target
   if (!pred || !target || !labels || !strides || !sums2 || !ws || N <= 0 || X <= 0) return SOD_EARG;
   RpBoxArgs a{pred, target, labels, strides, N, X, bg_label, beta};
   hipStream_t st = (hipStream_t)stream;
-  const int g = rp_nblk((long long)N * X);
+  const int g = sod_nblk((long long)N * X);
   SOD_LAUNCH(rp_box_loss_kernel<false>, dim3(g), dim3(256), 0, st, a, ws, nullptr, nullptr, 0.f, 0.f, nullptr);
-  SOD_LAUNCH(rp_box_finish_kernel, dim3(1), dim3(256), 0, st, ws, g, sums2);
+  SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 2, sums2, 0);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }
@@ -548,7 +530,7 @@ extern "C" int sod_reppoints_box_loss_bwd(const float* pred, const float* target
                                           float* dpred, void* stream) {
   if (!pred || !target || !labels || !strides || !grad_num || !grad_den || !dpred || N <= 0 || X <= 0) return SOD_EARG;
   RpBoxArgs a{pred, target, labels, strides, N, X, bg_label, beta};
-  SOD_LAUNCH(rp_box_loss_kernel<true>, dim3(rp_nblk((long long)N * X, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den,
+  SOD_LAUNCH(rp_box_loss_kernel<true>, dim3(sod_nblk((long long)N * X, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den,
              den_min, mul, dpred);
   SOD_CHECK_LAUNCH();
   return SOD_OK;

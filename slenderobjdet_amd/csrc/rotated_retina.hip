@@ -5,7 +5,6 @@
 //     two launches (image = grid.y, the image's gt count read on the device).  Decision-identical to sod_anchor_match_rotated ->
 //     sod_retina_targets' mapping -> sod_box2box_get_deltas per image: the same iou_rotated_lds, the same 64-bit "first maximum wins".
 //     sod_retina_label_rotated_boxes: the same kernels writing the matched gt box itself instead of the deltas (the rotated IoU loss).
-//   * sod_retina_box5_loss_*: retina_box_kernel of detection_ops.hip for 5 deltas per anchor (anchor a of pixel p at p*pitch + a*5).
 //   * sod_retina_decode_rotated: Box2BoxTransformRotated.apply_deltas on the candidates of sod_dense_topk_select, one launch per batch.
 // Latency / HBM-bound fp32 work, no MFMA; the clipping's candidate points live in LDS (rotated_iou.h).
 #include "common.h"
@@ -15,20 +14,10 @@
 namespace {
 
 #include "rotated_iou.h"
+#include "box_transform.h"
 
-constexpr int RR_RED = 1024;
-constexpr float RR_PI = 3.14159265358979323846f;
 constexpr int RR_GS = 8;                  // boxes per round of the labeller: at most 256 * RR_GS candidate pairs
 constexpr int RR_MAX_LEVELS = 8;
-
-inline int rr_nblk(long long n, int cap = RR_RED) {
-  long long g = (n + 255) / 256;
-  if (g > cap) g = cap;
-  if (g < 1) g = 1;
-  return (int)g;
-}
-
-struct RW5 { float w[5]; };
 
 struct LabelArgs {
   const float* anchors;      // (R, 5)
@@ -38,7 +27,7 @@ struct LabelArgs {
   int R, Gmax;
   float lo, hi;
   int l0, l1, l2, low_quality, num_classes;
-  RW5 w;
+  W5 w;
   int* labels;               // (N, R)
   float* deltas;             // (N, R, 5): the deltas, or the matched gt boxes (retina_label1_rot_kernel<true>)
   unsigned* gt_best;         // (N, Gmax) IoU bits, zeroed by the call
@@ -124,14 +113,8 @@ __global__ __launch_bounds__(256) void retina_label1_rot_kernel(const LabelArgs 
         if constexpr (BOXES) {
 #pragma unroll
           for (int e = 0; e < 5; ++e) d[e] = t[e];
-        } else {                          // Box2BoxTransformRotated.get_deltas, as get_deltas_kernel of rcnn_ops.hip
-          d[0] = a.w.w[0] * (t[0] - s[0]) / s[2]; d[1] = a.w.w[1] * (t[1] - s[1]) / s[3];
-          d[2] = a.w.w[2] * logf(t[2] / s[2]); d[3] = a.w.w[3] * logf(t[3] / s[3]);
-          float da = t[4] - s[4];
-          da = fmodf(da + 180.f, 360.f);
-          if (da < 0.f) da += 360.f;          // python's % (result takes the sign of the divisor)
-          da -= 180.f;
-          d[4] = da * a.w.w[4] * RR_PI / 180.f;
+        } else {
+          rot_get_deltas(s, t, a.w.w, d);
         }
       }
       labels[i] = lab;
@@ -201,67 +184,6 @@ __global__ __launch_bounds__(256) void retina_label2_rot_kernel(const LabelArgs 
   }
 }
 
-// ---------------------------------------------------------------------------------------------- smooth-L1 over 5 deltas
-struct Box5Args {
-  const float* pred;        // (N, sumHW, pitch) fp32: anchor a of pixel p at p*pitch + a*5
-  const int* labels;        // (N, R)
-  const float* deltas;      // (N, R, 5)
-  int N, R, A, pitch, num_classes;
-  float beta;
-};
-
-template <bool BWD, typename T = __bf16>      // T: storage type of the delta gradient (bf16 product path, float in the fp32 validation mode)
-__global__ __launch_bounds__(256) void retina_box5_kernel(const Box5Args a, float* __restrict__ part, const float* __restrict__ gnum,
-                                                          const float* __restrict__ gden, T* __restrict__ dpred) {
-  __shared__ float red[4];
-  float acc = 0.f, npos = 0.f;
-  const float sc = BWD ? gnum[0] / gden[0] : 0.f;
-  const long long total = (long long)a.N * a.R;
-  const long long pix_per_img = a.R / a.A;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += (long long)gridDim.x * 256) {
-    const long long n = i / a.R, r = i - n * a.R;
-    const long long px = r / a.A;
-    const int an = (int)(r - px * a.A);
-    const long long po = (n * pix_per_img + px) * a.pitch + an * 5;
-    const int lab = a.labels[i];
-    const bool pos = lab >= 0 && lab != a.num_classes;
-    float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (pos) {
-      npos += 1.f;
-#pragma unroll
-      for (int e = 0; e < 5; ++e) {
-        const float d = a.pred[po + e] - a.deltas[i * 5 + e], ad = fabsf(d);
-        if (a.beta < 1e-5f) { acc += ad; g[e] = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-        else if (ad < a.beta) { acc += 0.5f * d * d / a.beta; g[e] = d / a.beta; }
-        else { acc += ad - 0.5f * a.beta; g[e] = d > 0.f ? 1.f : -1.f; }
-      }
-    }
-    if (BWD) {
-#pragma unroll
-      for (int e = 0; e < 5; ++e) dpred[po + e] = (T)(g[e] * sc);
-    }
-  }
-  if (!BWD) {
-    acc = block_sum_256(acc, red);
-    npos = block_sum_256(npos, red);
-    if (threadIdx.x == 0) { part[blockIdx.x] = acc; part[RR_RED + blockIdx.x] = npos; }
-  }
-}
-
-// sums[0] = smooth-L1 sum over positives, sums[1] = number of positives; normalizer <- m*normalizer + (1-m)*max(npos,1)
-__global__ void retina_box5_finish_kernel(const float* __restrict__ part, int nblk_, float* __restrict__ sums, float* __restrict__ normalizer,
-                                          float momentum) {
-  __shared__ float red[4];
-  float a = 0.f, b = 0.f;
-  for (int i = threadIdx.x; i < nblk_; i += 256) { a += part[i]; b += part[RR_RED + i]; }
-  a = block_sum_256(a, red);
-  b = block_sum_256(b, red);
-  if (threadIdx.x == 0) {
-    sums[0] = a; sums[1] = b;
-    if (normalizer) normalizer[0] = momentum * normalizer[0] + (1.f - momentum) * fmaxf(b, 1.f);
-  }
-}
-
 // ---------------------------------------------------------------------------------------------- decode
 struct DecodeArgs {
   const float* pred;        // (N, P, pitch)
@@ -270,7 +192,7 @@ struct DecodeArgs {
   const float* scores;      // (N, M), -inf = empty slot
   int N, P, A, pitch, M, top_n;
   int row0[RR_MAX_LEVELS];  // first anchor of each level
-  RW5 w;
+  W5 w;
   float clampv;
   float* out;               // (N, M, 5)
 };
@@ -287,15 +209,7 @@ __global__ __launch_bounds__(256) void retina_decode_rot_kernel(const DecodeArgs
       const int an = (int)(r - px * a.A);
       const float* d = a.pred + (n * a.P + px) * a.pitch + an * 5;
       const float* b = a.anchors + r * 5;
-      // Box2BoxTransformRotated.apply_deltas, as apply_deltas_kernel of rcnn_ops.hip
-      const float dx = d[0] / a.w.w[0], dy = d[1] / a.w.w[1], dw = fminf(d[2] / a.w.w[2], a.clampv), dh = fminf(d[3] / a.w.w[3], a.clampv);
-      const float da = d[4] / a.w.w[4];
-      o[0] = dx * b[2] + b[0]; o[1] = dy * b[3] + b[1];
-      o[2] = expf(dw) * b[2]; o[3] = expf(dh) * b[3];
-      float ang = da * 180.f / RR_PI + b[4];
-      ang = fmodf(ang + 180.f, 360.f);
-      if (ang < 0.f) ang += 360.f;
-      o[4] = ang - 180.f;
+      rot_apply_deltas(d, b, a.w.w, a.clampv, o);      // a NaN dw / dh is clamped away, any other NaN zeroes the box
       if (!(isfinite(o[0]) && isfinite(o[1]) && isfinite(o[2]) && isfinite(o[3]) && isfinite(o[4]))) {
 #pragma unroll
         for (int e = 0; e < 5; ++e) o[e] = 0.f;
@@ -304,15 +218,6 @@ __global__ __launch_bounds__(256) void retina_decode_rot_kernel(const DecodeArgs
 #pragma unroll
     for (int e = 0; e < 5; ++e) a.out[i * 5 + e] = o[e];
   }
-}
-
-inline bool fill_w5(RW5& w, const float* weights) {
-  if (!weights) return false;
-  for (int i = 0; i < 5; ++i) {
-    if (!(weights[i] > 0.f)) return false;
-    w.w[i] = weights[i];
-  }
-  return true;
 }
 
 inline bool matcher_label(int l) { return l >= -1 && l <= 1; }
@@ -339,7 +244,7 @@ static int label_rotated(const float* anchors, int R, const float* gt_boxes, con
   a.lo = thr_lo; a.hi = thr_hi; a.l0 = label_below; a.l1 = label_between; a.l2 = label_above;
   a.low_quality = (allow_low_quality && Gmax > 0) ? 1 : 0;
   a.num_classes = num_classes; a.labels = gt_labels; a.deltas = gt_deltas; a.gt_best = gt_best_ws;
-  const dim3 grid(rr_nblk(R, 2048), N);
+  const dim3 grid(sod_nblk(R, 2048), N);
   const size_t lds = sizeof(unsigned) * (Gmax > 0 ? Gmax : 1);
   SOD_LAUNCH(retina_label1_rot_kernel<BOXES>, grid, dim3(256), lds, st, a);
   if (a.low_quality) SOD_LAUNCH(retina_label2_rot_kernel, grid, dim3(256), lds, st, a);
@@ -363,46 +268,6 @@ extern "C" int sod_retina_label_rotated_boxes(const float* anchors, int R, const
                              allow_low_quality, num_classes, weights5, gt_labels, matched_boxes, gt_best_ws, stream);
 }
 
-static int box5_fill(Box5Args& a, const float* pred, int pitch, const int* labels, const float* deltas, int N, int R, int A, int K, float beta) {
-  if (!pred || !labels || !deltas || N <= 0 || R <= 0 || A <= 0 || R % A || pitch < A * 5) return SOD_EARG;
-  a = Box5Args{pred, labels, deltas, N, R, A, pitch, K, beta};
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box5_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                        int num_classes, float beta, float* sums2, float* normalizer, float momentum, float* ws, void* stream) {
-  Box5Args a{};
-  int rc = box5_fill(a, pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta);
-  if (rc || !sums2 || !ws) return rc ? rc : SOD_EARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = rr_nblk((long long)N * R);
-  SOD_LAUNCH((retina_box5_kernel<false, __bf16>), dim3(g), dim3(256), 0, st, a, ws, nullptr, nullptr, nullptr);
-  SOD_LAUNCH(retina_box5_finish_kernel, dim3(1), dim3(256), 0, st, ws, g, sums2, normalizer, momentum);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box5_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                        int num_classes, float beta, const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream) {
-  Box5Args a{};
-  int rc = box5_fill(a, pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta);
-  if (rc || !grad_num || !grad_den || !dpred_bf16) return rc ? rc : SOD_EARG;
-  SOD_LAUNCH((retina_box5_kernel<true, __bf16>), dim3(rr_nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den,
-             (__bf16*)dpred_bf16);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
-extern "C" int sod_retina_box5_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* gt_deltas, int N, int R, int A,
-                                            int num_classes, float beta, const float* grad_num, const float* grad_den, float* dpred, void* stream) {
-  Box5Args a{};
-  int rc = box5_fill(a, pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta);
-  if (rc || !grad_num || !grad_den || !dpred) return rc ? rc : SOD_EARG;
-  SOD_LAUNCH((retina_box5_kernel<true, float>), dim3(rr_nblk((long long)N * R, 4096)), dim3(256), 0, (hipStream_t)stream, a, nullptr, grad_num, grad_den, dpred);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
-
 extern "C" int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors, const int* rows, const float* scores, int N, int P,
                                          int A, int M, int top_n, const int* level_row0, int nlev, const float* weights5, float scale_clamp,
                                          float* out, void* stream) {
@@ -417,7 +282,7 @@ extern "C" int sod_retina_decode_rotated(const float* pred, int pitch, const flo
   }
   a.pred = pred; a.anchors = anchors; a.rows = rows; a.scores = scores; a.N = N; a.P = P; a.A = A; a.pitch = pitch; a.M = M; a.top_n = top_n;
   a.clampv = scale_clamp; a.out = out;
-  SOD_LAUNCH(retina_decode_rot_kernel, dim3(rr_nblk((long long)N * M, 4096)), dim3(256), 0, (hipStream_t)stream, a);
+  SOD_LAUNCH(retina_decode_rot_kernel, dim3(sod_nblk((long long)N * M, 4096)), dim3(256), 0, (hipStream_t)stream, a);
   SOD_CHECK_LAUNCH();
   return SOD_OK;
 }

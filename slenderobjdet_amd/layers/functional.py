@@ -1373,16 +1373,69 @@ def retina_targets(anchors, gt_boxes, gt_classes, matches, match_labels, num_cla
          ptr(gt_deltas_out), stream_ptr())
 
 
-def retina_box_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, normalizer, momentum):
+# The fused box regression loss on the pitched delta buffer (csrc/retina_box_loss.hip), four kinds: smooth-L1 over D = 4 ("box") or 5
+# ("box5") deltas against the matched deltas; GIoU (D = 4, "giou") and rotated IoU (D = 5, "riou") of the decoded box against the matched
+# gt box.  A kind's extra arguments follow the target: (beta,) or (anchors, weights, scale_clamp).
+def _retina_loss_args(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, dpred=None):
+    """Checks the buffers against N, R, A and pitch - the kernels index by those integers alone - and returns the C arguments up to the
+    kind's extras.  The keep-alive of the weights' ctypes array is the returned list itself."""
+    anchors = extra[0] if len(extra) == 3 else None
+    for t, dt, name in ((pred, torch.float32, "pred"), (gt_labels, torch.int32, "gt_labels"), (target, torch.float32, "target"),
+                        (anchors, torch.float32, "anchors"), (dpred, ACT_DTYPE, "dpred")):
+        _chk(t, dt, name)
+    if not (A > 0 and R % A == 0 and pitch >= A * D and pred.numel() == N * (R // A) * pitch and gt_labels.numel() == N * R
+            and target.numel() == N * R * D and (anchors is None or (tuple(anchors.shape) == (R, D) and len(extra[1]) == D))
+            and (dpred is None or dpred.numel() == pred.numel())):
+        raise _C.SlenderHipError(f"retina_{stem}_loss: pred (and dpred) (N, R / A, pitch >= A * {D}), gt_labels (N, R), target (N, R, {D})"
+                                 + (f", anchors (R, {D}), {D} weights" if anchors is not None else ""))
+    args = [ptr(pred), pitch, ptr(gt_labels)] + ([ptr(anchors)] if anchors is not None else []) + [ptr(target), N, R, A, num_classes]
+    return args + ([float(extra[0])] if anchors is None else [_float_arr(extra[1]), float(extra[2])])
+
+
+def _retina_loss_fwd(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, normalizer, momentum):
+    """Advances the EMA normaliser; returns [loss summed over the positives, num_pos]."""
+    args = _retina_loss_args(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes)
     sums = torch.empty(2, dtype=torch.float32, device=pred.device)
-    call("sod_retina_box_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta), ptr(sums),
-         ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
+    call(f"sod_retina_{stem}_loss_fwd", *args, ptr(sums), ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
     return sums
 
 
+def _retina_loss_bwd(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, grad_num, grad_den, dpred):
+    """Writes every element of dpred: grad_num / grad_den times the delta gradient at the positives, zeros elsewhere (pad columns too)."""
+    args = _retina_loss_args(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, dpred)
+    call(f"sod_retina_{stem}_loss_bwd" + ("_f32" if is_f32() else ""), *args, ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
+
+
+def retina_box_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, normalizer, momentum):
+    return _retina_loss_fwd("box", 4, (beta,), pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, normalizer, momentum)
+
+
 def retina_box_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, grad_num, grad_den, dpred):
-    call("sod_retina_box_loss_bwd_f32" if is_f32() else "sod_retina_box_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta), ptr(grad_num),
-         ptr(grad_den), ptr(dpred), stream_ptr())
+    _retina_loss_bwd("box", 4, (beta,), pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, grad_num, grad_den, dpred)
+
+
+def retina_box5_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, normalizer, momentum):
+    return _retina_loss_fwd("box5", 5, (beta,), pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, normalizer, momentum)
+
+
+def retina_box5_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, grad_num, grad_den, dpred):
+    _retina_loss_bwd("box5", 5, (beta,), pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, grad_num, grad_den, dpred)
+
+
+def retina_giou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
+    return _retina_loss_fwd("giou", 4, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, normalizer, momentum)
+
+
+def retina_giou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
+    _retina_loss_bwd("giou", 4, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
+
+
+def retina_riou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
+    return _retina_loss_fwd("riou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, normalizer, momentum)
+
+
+def retina_riou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
+    _retina_loss_bwd("riou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
 
 
 # ----------------------------------------------------------------------------------------------- RotatedRetinaNet
@@ -1413,18 +1466,6 @@ def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, l
     return gt_labels, gt_deltas
 
 
-def retina_box5_loss_fwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, normalizer, momentum):
-    sums = torch.empty(2, dtype=torch.float32, device=pred.device)
-    call("sod_retina_box5_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta), ptr(sums),
-         ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
-    return sums
-
-
-def retina_box5_loss_bwd(pred, pitch, gt_labels, gt_deltas, N, R, A, num_classes, beta, grad_num, grad_den, dpred):
-    call("sod_retina_box5_loss_bwd_f32" if is_f32() else "sod_retina_box5_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(gt_deltas), N, R, A, num_classes, float(beta),
-         ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
-
-
 def rotated_iou_loss_fwd(pred, target, want_elem=True):
     """1 - IoU of the pairs (pred[i], target[i]) of (P, 5) boxes (cx, cy, w, h, angle_deg) -> (elem (P) or None, sum (1)); the IoU is
     box_iou_rotated's, to the bit."""
@@ -1446,36 +1487,6 @@ def rotated_iou_loss_bwd(pred, target, grad_scale=None):
     d = torch.empty_like(pred)
     call("sod_rotated_iou_loss", ptr(pred), ptr(target), pred.shape[0], None, None, ptr(grad_scale), ptr(d), None, stream_ptr())
     return d
-
-
-def _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights):
-    """The kernels index by N, R, A and pitch alone: the buffers must have exactly those sizes."""
-    _chk(pred, torch.float32, "pred"); _chk(gt_labels, torch.int32, "gt_labels"); _chk(anchors, torch.float32, "anchors")
-    _chk(matched_boxes, torch.float32, "matched_boxes")
-    if (len(weights) != 5 or A <= 0 or R % A or pitch < A * 5 or pred.numel() != N * (R // A) * pitch or gt_labels.numel() != N * R
-            or tuple(anchors.shape) != (R, 5) or matched_boxes.numel() != N * R * 5):
-        raise _C.SlenderHipError("retina_riou_loss: pred (N, R / A, pitch >= A * 5), gt_labels (N, R), anchors (R, 5), matched_boxes (N, R, 5), five weights")
-
-
-def retina_riou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
-    """Rotated IoU box regression of RotatedRetinaNet on the pitched delta buffer (five deltas per anchor); advances the EMA normaliser;
-    returns [sum of 1 - IoU over the positives, num_pos]."""
-    _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights)
-    sums = torch.empty(2, dtype=torch.float32, device=pred.device)
-    w = _float_arr(weights)
-    call("sod_retina_riou_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
-         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(sums), ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
-    return sums
-
-
-def retina_riou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
-    _riou_chk(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, weights)
-    _chk(dpred, ACT_DTYPE, "dpred")
-    if dpred.numel() != pred.numel():
-        raise _C.SlenderHipError("retina_riou_loss: dpred must have the prediction buffer's shape")
-    w = _float_arr(weights)
-    call("sod_retina_riou_loss_bwd_f32" if is_f32() else "sod_retina_riou_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
-         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
 
 
 def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):
@@ -1870,21 +1881,6 @@ def bce_logits_soft_bwd(logits, targets, labels, bg_label, grad_scale, scale_mul
     call("sod_bce_logits_soft_bwd", ptr(logits), ptr(targets), ptr(labels), int(bg_label), logits.numel(), ptr(grad_scale), float(scale_mul), ptr(d),
          stream_ptr())
     return d
-
-
-def retina_giou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
-    """GIoU box regression of RetinaNet / AnchorHead on the pitched delta buffer; advances the EMA normaliser; returns [sum, num_pos]."""
-    sums = torch.empty(2, dtype=torch.float32, device=pred.device)
-    w = _float_arr(weights)
-    call("sod_retina_giou_loss_fwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
-         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(sums), ptr(normalizer), float(momentum), ptr(reduce_ws(pred.device)), stream_ptr())
-    return sums
-
-
-def retina_giou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
-    w = _float_arr(weights)
-    call("sod_retina_giou_loss_bwd_f32" if is_f32() else "sod_retina_giou_loss_bwd", ptr(pred), pitch, ptr(gt_labels), ptr(anchors), ptr(matched_boxes), N, R, A, num_classes,
-         ctypes.cast(w, ctypes.c_void_p), float(scale_clamp), ptr(grad_num), ptr(grad_den), ptr(dpred), stream_ptr())
 
 
 # ---- fp32 validation mode: the wrappers of the training step dispatch to functional_f32 when it is on; everything that only the bf16

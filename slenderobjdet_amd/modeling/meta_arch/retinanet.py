@@ -90,6 +90,17 @@ class RetinaNetHead(nn.Module):
         return cls_buf, box_buf, hw, offs
 
 
+def _box_loss_kind(model, hw):
+    """The model's box regression loss as the leading arguments of HF._retina_loss_fwd / _bwd: (symbol stem, deltas per anchor, the
+    kind's extra arguments).  For the two IoU kinds the targets (``gt_deltas``) hold the matched gt BOXES (N, R, D)."""
+    if model.box_reg_loss_type == "giou":
+        return "giou", 4, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
+    if model.box_reg_loss_type == "rotated_iou":        # RotatedRetinaNet
+        return "riou", 5, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
+    D = getattr(model.head, "box_dim", 4)
+    return ("box5" if D == 5 else "box"), D, (model.smooth_l1_loss_beta,)
+
+
 class _RetinaLossFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, model, weight, gt_labels, gt_deltas, *towers):
@@ -100,16 +111,8 @@ class _RetinaLossFn(torch.autograd.Function):
         N, P = cls_buf.shape[0], cls_buf.shape[1]
         A, K = head.num_anchors, head.num_classes
         R = P * A
-        if model.box_reg_loss_type == "giou":       # gt_deltas then holds the matched gt BOXES (N,R,4)
-            sums = HF.retina_giou_loss_fwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
-                                           model.scale_clamp, model.loss_normalizer, model.loss_normalizer_momentum)
-        elif model.box_reg_loss_type == "rotated_iou":      # RotatedRetinaNet: gt_deltas holds the matched gt BOXES (N,R,5)
-            sums = HF.retina_riou_loss_fwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
-                                           model.scale_clamp, model.loss_normalizer, model.loss_normalizer_momentum)
-        else:
-            box_loss_fwd = HF.retina_box5_loss_fwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_fwd
-            sums = box_loss_fwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta,
-                                          model.loss_normalizer, model.loss_normalizer_momentum)    # also advances the EMA normaliser
+        sums = HF._retina_loss_fwd(*_box_loss_kind(model, hw), box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K,
+                                   model.loss_normalizer, model.loss_normalizer_momentum)    # also advances the EMA normaliser
         dcls_u = None
         # the one-pass kernel is vectorised only (sod_sigmoid_focal_loss_fwd_grad: 4 classes per lane, 32-bit element offsets): other
         # layouts (NUM_CLASSES % 4 != 0, N * R * K >= 2^31) take the two-pass entry points as before round 4
@@ -150,15 +153,7 @@ class _RetinaLossFn(torch.autograd.Function):
                                                 scale_num=g2[0:1], scale_den=norm, den_mul=1.0, den_min=1e-12,
                                                 out_bf16=not HF.is_f32()).view(N, P, head.kc), None
         dbox = torch.zeros((N, P, head.box_pitch), dtype=HF.ACT_DTYPE, device=dev)
-        if model.box_reg_loss_type == "giou":
-            HF.retina_giou_loss_bwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
-                                    model.scale_clamp, g2[1:2], norm, dbox)
-        elif model.box_reg_loss_type == "rotated_iou":
-            HF.retina_riou_loss_bwd(box_buf, head.box_pitch, gt_labels, model.anchors_for(hw), gt_deltas, N, R, A, K, model.bbox_reg_weights,
-                                    model.scale_clamp, g2[1:2], norm, dbox)
-        else:
-            box_loss_bwd = HF.retina_box5_loss_bwd if getattr(head, "box_dim", 4) == 5 else HF.retina_box_loss_bwd
-            box_loss_bwd(box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, model.smooth_l1_loss_beta, g2[1:2], norm, dbox)
+        HF._retina_loss_bwd(*_box_loss_kind(model, hw), box_buf, head.box_pitch, gt_labels, gt_deltas, N, R, A, K, g2[1:2], norm, dbox)
         grads = []
         for pred, dbuf, kk, tower, scale in ((head.cls_score, dcls, head.kc, cls_t, cls_scale), (head.bbox_pred, dbox, head.box_pitch, box_t, None)):
             dys = [dbuf.view(-1)[o * kk:] for o in offs]
