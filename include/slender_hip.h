@@ -575,7 +575,7 @@ int sod_f32_to_bf16(const float* x, void* y, long long n, void* stream);
  * sod_retina_box_loss_* = smooth_l1_loss(pred_deltas[pos], gt_deltas[pos], beta, "sum") (:229) on the pitched prediction buffer
  * (anchor a of pixel p at p*pitch + a*4) + the EMA loss normaliser (:210-214) kept on the device:
  * normalizer <- momentum*normalizer + (1-momentum)*max(num_pos,1); sums2 = {loss sum, num_pos}.
- * The contract of all four fused box losses (csrc/retina_box_loss.hip: sod_retina_{box,box5,giou,riou}_loss_*, D = 4, 5, 4, 5 deltas per
+ * The contract of all five fused box losses (csrc/retina_box_loss.hip: sod_retina_{box,box5,giou,riou,rgiou}_loss_*, D = 4, 5, 4, 5, 5 deltas per
  * anchor), said once: pred and dpred are (N, R / A, pitch) with pitch >= A*D, gt_labels (N, R), the target (N, R, D); the sizes are not
  * checked beyond that (the caller's job); positives are 0 <= label != num_classes.  bwd writes EVERY element of every pixel's pitch-wide
  * row of dpred (bf16, or fp32 for *_bwd_f32): grad_num[0] / grad_den[0] * d sum / d pred in the D columns of a positive, exact zeros in
@@ -956,6 +956,26 @@ int sod_retina_label_rotated_boxes(const float* anchors, int R, const float* gt_
                                    int N, int Gmax, float thr_lo, float thr_hi, int label_below, int label_between, int label_above,
                                    int allow_low_quality, int num_classes, const float* weights5, int* gt_labels,
                                    float* matched_boxes, unsigned* gt_best_ws, void* stream);
+
+/* Rotated GIoU box loss (layers.rotated_giou_loss, BBOX_REG_LOSS_TYPE "rotated_giou"): loss = 1 - IoU + (C - U) / C in [0, 2) with
+ * U = area1 + area2 - I the union and C the area of the convex hull of the 8 corners (csrc/box_pair_loss.h: rgiou_pair).  The IoU is
+ * the same number as above, to the bit; I and U are recovered from it (IoU == 0: I = 0).  A pair without overlap keeps a gradient, the
+ * hull term's.  C <= 0 (both boxes degenerate): no hull term.  The hull is walked in registers over the corners sorted by (x, y); of
+ * collinear candidates the farthest is the next vertex, of coincident ones the first (the target's before the prediction's), and the
+ * gradient is that of the shoelace sum over the walked vertices - at such a tie a one-sided derivative.  Besides the kinks of the IoU
+ * the loss has kinks where a corner enters or leaves the hull.
+ * sod_rotated_giou_loss: the contract of sod_rotated_iou_loss.  sod_retina_rgiou_loss_{fwd,bwd,bwd_f32}: that of sod_retina_riou_loss_*. */
+int sod_rotated_giou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
+                          const float* grad_scale, float* dboxes1, float* ws, void* stream);
+int sod_retina_rgiou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                              int N, int R, int A, int num_classes, const float* weights5, float scale_clamp, float* sums2,
+                              float* normalizer, float momentum, float* ws, void* stream);
+int sod_retina_rgiou_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                              int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                              const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream);
+int sod_retina_rgiou_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                  int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                  const float* grad_num, const float* grad_den, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Minimum-area rectangles of polygon annotations (csrc/polygon_geom.hip; host side slenderobjdet_amd/structures/polygons.py): the

@@ -6,6 +6,7 @@
 //   SmoothL1Loss<5>  sod_retina_box5_loss_*   the same over five deltas
 //   GiouLoss         sod_retina_giou_loss_*   Box2BoxTransform.apply_deltas, fvcore giou_loss against the matched gt box          ("giou")
 //   RiouLoss         sod_retina_riou_loss_*   Box2BoxTransformRotated.apply_deltas, 1 - rotated IoU against the matched gt box    ("rotated_iou")
+//   RgiouLoss        sod_retina_rgiou_loss_*  the same decode, 1 - IoU + (hull - union) / hull against the matched gt box         ("rotated_giou")
 // A policy has: D; Args (BoxLossArgs plus its own fields); ROT_LDS (whether the kernel owns the 48 KB of clipping points of rotated_iou.h);
 // and positive<BWD>(a, p, r, i, pts, acc, g): for the positive anchor i = n*R + r whose deltas start at p, add the loss to acc (in place:
 // smooth-L1 adds element by element, and the running sum's bits depend on that) and, if BWD, write the D delta gradients to g (zeros before).
@@ -82,7 +83,9 @@ struct GiouLoss {
 };
 
 // The IoU is iou_rotated_lds (the number NMS, the matcher and the evaluator see); a positive whose IoU is 0 has no gradient.
-struct RiouLoss {
+// HULL: with the hull term of rgiou_pair, which leaves such a positive a gradient.
+template <bool HULL>
+struct RotIouLoss {
   static constexpr int D = 5;
   static constexpr bool ROT_LDS = true;
   using Args = DecodeLossArgs;
@@ -93,10 +96,11 @@ struct RiouLoss {
     for (int e = 0; e < 5; ++e) { d[e] = p[e]; s[e] = a.anchors[r * 5 + e]; t[e] = a.target[i * 5 + e]; }
     const RotDecoded k = rot_apply_deltas(d, s, a.w.w, a.clampv, box);
     const float iou = iou_rotated_lds(box, t, pts, 256);
-    acc += 1.f - iou;
-    if (BWD && iou > 0.f) {
-      float gb[5];
-      riou_grad(box, t, iou, gb);
+    float gb[5];
+    if constexpr (HULL) acc += rgiou_pair<BWD>(box, t, iou, gb);
+    else acc += 1.f - iou;
+    if (BWD && (HULL || iou > 0.f)) {
+      if constexpr (!HULL) riou_grad(box, t, iou, gb);
       g[0] = gb[0] * s[2] / a.w.w[0];
       g[1] = gb[1] * s[3] / a.w.w[1];
       g[2] = k.cw ? 0.f : gb[2] * box[2] / a.w.w[2];
@@ -105,6 +109,8 @@ struct RiouLoss {
     }
   }
 };
+using RiouLoss = RotIouLoss<false>;
+using RgiouLoss = RotIouLoss<true>;
 
 // T: storage type of the delta gradient (bf16 product path, float in the fp32 validation mode)
 template <class Loss, bool BWD, typename T>
@@ -271,4 +277,23 @@ extern "C" int sod_retina_riou_loss_bwd_f32(const float* pred, int pitch, const 
                                             const float* grad_num, const float* grad_den, float* dpred, void* stream) {
   DECODE_FILL(5, weights5);
   return launch_bwd<RiouLoss>(a, grad_num, grad_den, dpred, stream);
+}
+
+extern "C" int sod_retina_rgiou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                         int N, int R, int A, int num_classes, const float* weights5, float scale_clamp, float* sums2,
+                                         float* normalizer, float momentum, float* ws, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_fwd<RgiouLoss>(a, sums2, normalizer, momentum, ws, stream);
+}
+extern "C" int sod_retina_rgiou_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                         int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                         const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_bwd<RgiouLoss>(a, grad_num, grad_den, (__bf16*)dpred_bf16, stream);
+}
+extern "C" int sod_retina_rgiou_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                             int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                             const float* grad_num, const float* grad_den, float* dpred, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_bwd<RgiouLoss>(a, grad_num, grad_den, dpred, stream);
 }

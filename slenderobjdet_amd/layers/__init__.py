@@ -4,8 +4,8 @@
 def __getattr__(name):
     # ``from slenderobjdet_amd.layers import rotated_iou_loss`` without importing the loss module together with the package: what a
     # program loads when it imports a sub-module of ``layers`` stays what it was
-    if name == "rotated_iou_loss":
-        from .losses import rotated_iou_loss
+    if name in ("rotated_iou_loss", "rotated_giou_loss"):
+        from . import losses
 
-        return rotated_iou_loss
+        return getattr(losses, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

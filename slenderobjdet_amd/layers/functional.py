@@ -1373,9 +1373,9 @@ def retina_targets(anchors, gt_boxes, gt_classes, matches, match_labels, num_cla
          ptr(gt_deltas_out), stream_ptr())
 
 
-# The fused box regression loss on the pitched delta buffer (csrc/retina_box_loss.hip), four kinds: smooth-L1 over D = 4 ("box") or 5
-# ("box5") deltas against the matched deltas; GIoU (D = 4, "giou") and rotated IoU (D = 5, "riou") of the decoded box against the matched
-# gt box.  A kind's extra arguments follow the target: (beta,) or (anchors, weights, scale_clamp).
+# The fused box regression loss on the pitched delta buffer (csrc/retina_box_loss.hip), five kinds: smooth-L1 over D = 4 ("box") or 5
+# ("box5") deltas against the matched deltas; GIoU (D = 4, "giou"), rotated IoU (D = 5, "riou") and rotated GIoU (D = 5, "rgiou") of the
+# decoded box against the matched gt box.  A kind's extra arguments follow the target: (beta,) or (anchors, weights, scale_clamp).
 def _retina_loss_args(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, dpred=None):
     """Checks the buffers against N, R, A and pitch - the kernels index by those integers alone - and returns the C arguments up to the
     kind's extras.  The keep-alive of the weights' ctypes array is the returned list itself."""
@@ -1438,6 +1438,14 @@ def retina_riou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A
     _retina_loss_bwd("riou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
 
 
+def retina_rgiou_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
+    return _retina_loss_fwd("rgiou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, normalizer, momentum)
+
+
+def retina_rgiou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
+    _retina_loss_bwd("rgiou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
+
+
 # ----------------------------------------------------------------------------------------------- RotatedRetinaNet
 def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, labels, allow_low_quality, num_classes, weights, ws=None,
                          want_boxes=False):
@@ -1466,27 +1474,46 @@ def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, l
     return gt_labels, gt_deltas
 
 
-def rotated_iou_loss_fwd(pred, target, want_elem=True):
-    """1 - IoU of the pairs (pred[i], target[i]) of (P, 5) boxes (cx, cy, w, h, angle_deg) -> (elem (P) or None, sum (1)); the IoU is
-    box_iou_rotated's, to the bit."""
+def _rotated_pair_loss_fwd(stem, pred, target, want_elem):
     _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target")
     if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
-        raise _C.SlenderHipError("rotated_iou_loss: pred and target must both be (P, 5)")
+        raise _C.SlenderHipError(f"rotated_{stem}_loss: pred and target must both be (P, 5)")
     P = pred.shape[0]
     elem = torch.empty(P, dtype=torch.float32, device=pred.device) if want_elem else None
     s = torch.empty(1, dtype=torch.float32, device=pred.device)
-    call("sod_rotated_iou_loss", ptr(pred), ptr(target), P, ptr(elem), ptr(s), None, None, ptr(reduce_ws(pred.device)), stream_ptr())
+    call(f"sod_rotated_{stem}_loss", ptr(pred), ptr(target), P, ptr(elem), ptr(s), None, None, ptr(reduce_ws(pred.device)), stream_ptr())
     return elem, s
+
+
+def _rotated_pair_loss_bwd(stem, pred, target, grad_scale):
+    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target"); _chk(grad_scale, torch.float32, "grad_scale")
+    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
+        raise _C.SlenderHipError(f"rotated_{stem}_loss: pred and target must both be (P, 5)")
+    d = torch.empty_like(pred)
+    call(f"sod_rotated_{stem}_loss", ptr(pred), ptr(target), pred.shape[0], None, None, ptr(grad_scale), ptr(d), None, stream_ptr())
+    return d
+
+
+def rotated_iou_loss_fwd(pred, target, want_elem=True):
+    """1 - IoU of the pairs (pred[i], target[i]) of (P, 5) boxes (cx, cy, w, h, angle_deg) -> (elem (P) or None, sum (1)); the IoU is
+    box_iou_rotated's, to the bit."""
+    return _rotated_pair_loss_fwd("iou", pred, target, want_elem)
 
 
 def rotated_iou_loss_bwd(pred, target, grad_scale=None):
     """grad_scale[0] * d sum(1 - IoU) / d pred (P, 5), the angle's column per degree; rows without overlap (IoU exactly 0) are zero."""
-    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target"); _chk(grad_scale, torch.float32, "grad_scale")
-    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
-        raise _C.SlenderHipError("rotated_iou_loss: pred and target must both be (P, 5)")
-    d = torch.empty_like(pred)
-    call("sod_rotated_iou_loss", ptr(pred), ptr(target), pred.shape[0], None, None, ptr(grad_scale), ptr(d), None, stream_ptr())
-    return d
+    return _rotated_pair_loss_bwd("iou", pred, target, grad_scale)
+
+
+def rotated_giou_loss_fwd(pred, target, want_elem=True):
+    """1 - IoU + (C - U) / C of the pairs (pred[i], target[i]) of (P, 5) boxes, C the area of the convex hull of the 8 corners and U the
+    union -> (elem (P) or None, sum (1)); the IoU is rotated_iou_loss_fwd's, to the bit."""
+    return _rotated_pair_loss_fwd("giou", pred, target, want_elem)
+
+
+def rotated_giou_loss_bwd(pred, target, grad_scale=None):
+    """grad_scale[0] * d sum(loss) / d pred (P, 5), the angle's column per degree; rows without overlap keep the hull term's gradient."""
+    return _rotated_pair_loss_bwd("giou", pred, target, grad_scale)
 
 
 def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):

@@ -3,6 +3,7 @@
   sigmoid_focal_loss(_jit)  — fvcore.nn.sigmoid_focal_loss_jit as called at slender_det/modeling/meta_arch/fcos/fcosv2.py:124
   iou_loss                  — slender_det/layers/iou_loss.py:4-37
   rotated_iou_loss          — 1 - IoU of rotated box pairs (no counterpart in the reference), csrc/rotated_iou_loss.hip
+  rotated_giou_loss         — the same with the convex-hull term of GIoU, which keeps a gradient for pairs that do not overlap
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -101,12 +102,14 @@ def bce_with_logits_fg_sum(logits, targets, labels, bg_label):
 
 
 class _RotatedIouLossFn(torch.autograd.Function):
+    """``ops``: the (fwd, bwd) pair of the op layer - rotated IoU or rotated GIoU."""
+
     @staticmethod
-    def forward(ctx, pred, target, reduction):
+    def forward(ctx, pred, target, reduction, ops):
         p, t = pred.contiguous().float(), target.contiguous().float()
-        elem, s = HF.rotated_iou_loss_fwd(p, t, want_elem=(reduction == "none"))
+        elem, s = ops[0](p, t, want_elem=(reduction == "none"))
         ctx.save_for_backward(p, t)
-        ctx.reduction = reduction
+        ctx.reduction, ctx.bwd = reduction, ops[1]
         if reduction == "none":
             return elem.view(pred.shape[:-1])
         return s[0] / max(p.shape[0], 1) if reduction == "mean" else s[0]
@@ -116,20 +119,34 @@ class _RotatedIouLossFn(torch.autograd.Function):
     def backward(ctx, g):
         p, t = ctx.saved_tensors
         if ctx.reduction == "none":
-            return HF.rotated_iou_loss_bwd(p, t) * g.reshape(-1, 1).float(), None, None
+            return ctx.bwd(p, t) * g.reshape(-1, 1).float(), None, None, None
         scale = g.reshape(1).float().contiguous()
         if ctx.reduction == "mean":
             scale = scale / max(p.shape[0], 1)
-        return HF.rotated_iou_loss_bwd(p, t, grad_scale=scale), None, None
+        return ctx.bwd(p, t, grad_scale=scale), None, None, None
+
+
+def _rotated_pair_loss(name, ops, pred, target, reduction):
+    if reduction not in ("sum", "mean", "none"):
+        raise ValueError(f"{name}: reduction must be 'sum', 'mean' or 'none', got {reduction!r}")
+    if pred.dim() != 2 or pred.shape[-1] != 5 or pred.shape != target.shape:
+        raise ValueError(f"{name}: pred and target must both be (P, 5), got {tuple(pred.shape)} and {tuple(target.shape)}")
+    return _RotatedIouLossFn.apply(pred, target, reduction, ops)
 
 
 def rotated_iou_loss(pred, target, reduction="sum"):
     """1 - IoU(pred, target) of (P, 5) rotated boxes (cx, cy, w, h, angle_deg), the IoU being box_iou_rotated's (detectron2's); the
     gradient flows to ``pred`` only, its angle column per degree.  Boxes that do not overlap (IoU exactly 0) have loss 1 and NO gradient:
     use it on matched pairs (a positive anchor and its gt), not to pull distant boxes together.  The IoU has kinks where a vertex of one
-    box lies on an edge of the other and at identical boxes; the gradient there is the one of a side."""
-    if reduction not in ("sum", "mean", "none"):
-        raise ValueError(f"rotated_iou_loss: reduction must be 'sum', 'mean' or 'none', got {reduction!r}")
-    if pred.dim() != 2 or pred.shape[-1] != 5 or pred.shape != target.shape:
-        raise ValueError(f"rotated_iou_loss: pred and target must both be (P, 5), got {tuple(pred.shape)} and {tuple(target.shape)}")
-    return _RotatedIouLossFn.apply(pred, target, reduction)
+    box lies on an edge of the other and at identical boxes; the gradient there is the one of a side.  rotated_giou_loss is the loss
+    that keeps a gradient for boxes that do not overlap."""
+    return _rotated_pair_loss("rotated_iou_loss", (HF.rotated_iou_loss_fwd, HF.rotated_iou_loss_bwd), pred, target, reduction)
+
+
+def rotated_giou_loss(pred, target, reduction="sum"):
+    """1 - IoU + (C - U) / C of (P, 5) rotated boxes (cx, cy, w, h, angle_deg) in [0, 2): the IoU of rotated_iou_loss (to the bit), U the
+    union and C the area of the convex hull of the 8 corners.  The gradient flows to ``pred`` only, its angle column per degree; boxes
+    that do not overlap have loss 1 + (C - U) / C and the hull term's gradient, which pulls them together.  Besides the kinks of the
+    IoU the loss has kinks where a corner enters or leaves the hull (collinear or coincident corners: identical boxes, equal angles
+    with a shared edge line); the value is right there and the gradient is the one of a side (csrc/box_pair_loss.h says which)."""
+    return _rotated_pair_loss("rotated_giou_loss", (HF.rotated_giou_loss_fwd, HF.rotated_giou_loss_bwd), pred, target, reduction)

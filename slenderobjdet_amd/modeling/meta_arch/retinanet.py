@@ -92,11 +92,11 @@ class RetinaNetHead(nn.Module):
 
 def _box_loss_kind(model, hw):
     """The model's box regression loss as the leading arguments of HF._retina_loss_fwd / _bwd: (symbol stem, deltas per anchor, the
-    kind's extra arguments).  For the two IoU kinds the targets (``gt_deltas``) hold the matched gt BOXES (N, R, D)."""
+    kind's extra arguments).  For the IoU kinds the targets (``gt_deltas``) hold the matched gt BOXES (N, R, D)."""
     if model.box_reg_loss_type == "giou":
         return "giou", 4, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
-    if model.box_reg_loss_type == "rotated_iou":        # RotatedRetinaNet
-        return "riou", 5, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
+    if model.box_reg_loss_type in ("rotated_iou", "rotated_giou"):        # RotatedRetinaNet
+        return ("riou" if model.box_reg_loss_type == "rotated_iou" else "rgiou"), 5, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
     D = getattr(model.head, "box_dim", 4)
     return ("box5" if D == 5 else "box"), D, (model.smooth_l1_loss_beta,)
 

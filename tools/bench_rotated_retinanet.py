@@ -5,10 +5,10 @@ synthetic batches, bench.train_step with prefetch and the reference's warm-up sc
     on the same inputs, the two alternating; the labels of the two are compared first;
   * img/s of a full training step of the three classes, built one after the other in this process.
 Device events, warm-up, >= 20 timed calls; prints the card's shader clock with the figures.
-``--box-loss rotated_iou`` trains RotatedRetinaNet's box regression with the rotated IoU loss (MODEL.RETINANET.BBOX_REG_LOSS_TYPE)
-instead of smooth-L1; ``--rotated-only`` times RotatedRetinaNet's step alone (alternating runs of the two box losses, one process each).
+``--box-loss rotated_iou`` / ``rotated_giou`` trains RotatedRetinaNet's box regression with the rotated IoU / GIoU loss
+(MODEL.RETINANET.BBOX_REG_LOSS_TYPE) instead of smooth-L1; ``--rotated-only`` times RotatedRetinaNet's step alone (alternating runs of the two box losses, one process each).
 
-    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--box-loss smooth_l1|rotated_iou] [--rotated-only] [--out FILE]
+    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--box-loss smooth_l1|rotated_iou|rotated_giou] [--rotated-only] [--out FILE]
 """
 import argparse
 import json
@@ -30,7 +30,7 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--calls", type=int, default=20, help="timed calls per round of the labelling comparison (three rounds)")
 ap.add_argument("--skip-step", action="store_true", help="only the labelling comparison")
-ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou"], default="smooth_l1", help="RotatedRetinaNet's box regression loss")
+ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou"], default="smooth_l1", help="RotatedRetinaNet's box regression loss")
 ap.add_argument("--rotated-only", action="store_true", help="time RotatedRetinaNet's training step only, not the two other classes")
 ap.add_argument("--out", default=None, help="also write the JSON result to this file")
 args = ap.parse_args()
