@@ -2,8 +2,14 @@
 
 Restates detectron2's GeneralizedRCNN + RPN / RRPN + StandardROIHeads / RROIHeads (BASELINE config 5 =
 configs/rotated/faster_R_101.yaml over Base-RRCNN-FPN.yaml; the reference's own subclasses proposal_generator/rpn.py:26-356,
-roi_heads/roi_heads.py:27-66 build on them).  detectron2's source exists nowhere in this environment: every function here is
-"parity unpinned" against upstream and follows the contracts written down in SURVEY.md §2.3 / Appendix C.4-C.7, C.13-C.15.
+roi_heads/roi_heads.py:27-66 build on them).  detectron2's source exists nowhere in this environment: the functions follow the contracts
+written down in SURVEY.md §2.3 / Appendix C.4-C.7, C.13-C.15.
+
+Pinned by the reference's own Python (tests/golden/retina_rpn/, checked in tests/test_retina_rpn_golden_host.py, 4- and 5-column
+branches): rpn_match, rpn_losses (values, gradients, normaliser), the reshapes of rpn_outputs, apply_deltas / clip_boxes / nonempty as
+find_top_proposals uses them, find_top_proposals (order of top-k, finite filter, clip, small-box filter, per-level NMS, cut) and
+fast_rcnn_inference_single_image.  Unpinned ("parity unpinned" against upstream): fast_rcnn_losses, roi_pool / assign_levels (ROIPooler),
+roi_match, and the arithmetic of the restated third-party ops themselves (IoU, Matcher, Box2BoxTransform, NMS, smooth-L1).
 """
 import math
 
@@ -140,8 +146,11 @@ def rpn_losses(logits, deltas, gt_labels, gt_deltas, batch_size_per_image=256, b
     return {"loss_rpn_cls": cls / norm, "loss_rpn_loc": loc / norm}
 
 
-def find_top_proposals(props_l, logits_l, image_sizes, nms_thresh, pre_topk, post_topk, min_size=0.0):
-    """props_l / logits_l: per level (N, HWA, D) / (N, HWA). Returns per image (boxes, scores)."""
+def find_top_proposals(props_l, logits_l, image_sizes, nms_thresh, pre_topk, post_topk, min_size=0.0, training=False):
+    """props_l / logits_l: per level (N, HWA, D) / (N, HWA). Returns per image (boxes, scores).  Rows with a non-finite box or score are
+    dropped before the clip; with ``training=True`` they raise FloatingPointError instead (proposal_utils.py:96-105).  The default is
+    the eval-mode rule: a caller that restates a training step passes ``training=True`` (the only caller outside the golden tests,
+    tests/test_gpu_rcnn.py, runs the model in eval mode and says so)."""
     N = logits_l[0].shape[0]
     S, P, L = [], [], []
     for lvl, (p, lg) in enumerate(zip(props_l, logits_l)):
@@ -154,7 +163,13 @@ def find_top_proposals(props_l, logits_l, image_sizes, nms_thresh, pre_topk, pos
     S, P, L = torch.cat(S, 1), torch.cat(P, 1), torch.cat(L)
     out = []
     for n, size in enumerate(image_sizes):
-        b, s, l = clip_boxes(P[n], size), S[n], L
+        b, s, l = P[n], S[n], L
+        valid = torch.isfinite(b).all(dim=1) & torch.isfinite(s)
+        if not valid.all():
+            if training:
+                raise FloatingPointError("Predicted boxes or scores contain Inf/NaN. Training has diverged.")
+            b, s, l = b[valid], s[valid], l[valid]
+        b = clip_boxes(b, size)
         keep = nonempty(b, min_size)
         b, s, l = b[keep], s[keep], l[keep]
         keep = batched_nms_any(b, s, l, nms_thresh)[:post_topk]
@@ -203,16 +218,25 @@ def fast_rcnn_losses(scores, deltas, gt_classes, gt_deltas, num_classes, beta=0.
     return {"loss_cls": loss_cls, "loss_box_reg": loss_box}
 
 
-def fast_rcnn_inference_single_image(boxes, probs, image_size, score_thresh, nms_thresh, topk):
-    """boxes (R, K*D), probs (R, K+1)."""
+def fast_rcnn_inference_single_image(boxes, probs, image_size, score_thresh, nms_thresh, topk, D=None):
+    """boxes (R, K*D) class-specific or (R, D) class-agnostic, probs (R, K+1); ``D`` box columns (None: K*D columns are class-specific).
+    roi_heads/fast_rcnn.py:53-115: rows with a non-finite box or score are dropped first, a class-agnostic box serves every class,
+    ``topk`` < 0 keeps every survivor."""
+    valid = torch.isfinite(boxes).all(dim=1) & torch.isfinite(probs).all(dim=1)
+    if not valid.all():
+        boxes, probs = boxes[valid], probs[valid]
     K = probs.shape[1] - 1
-    D = boxes.shape[1] // K
+    if D is None:
+        D = boxes.shape[1] // K
+    C = boxes.shape[1] // D          # K class-specific boxes per row, or 1 class-agnostic box
     scores = probs[:, :-1]
-    b = clip_boxes(boxes.reshape(-1, D), image_size).view(-1, K, D)
+    b = clip_boxes(boxes.reshape(-1, D), image_size).view(-1, C, D)
     mask = scores > score_thresh
     inds = mask.nonzero()
-    b, s = b[mask], scores[mask]
-    keep = batched_nms_any(b, s, inds[:, 1], nms_thresh)[:topk]
+    b, s = (b[inds[:, 0], 0] if C == 1 else b[mask]), scores[mask]
+    keep = batched_nms_any(b, s, inds[:, 1], nms_thresh)
+    if topk >= 0:
+        keep = keep[:topk]
     return b[keep], s[keep], inds[keep, 1]
 
 

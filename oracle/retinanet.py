@@ -1,6 +1,12 @@
 """Oracle RetinaNet losses (CPU fp32): detectron2 RetinaNet.label_anchors / losses as documented by the reference's in-tree copy
 slender_det/modeling/meta_arch/retina/retina_rotated.py:185-295 (axis-aligned boxes), with Box2BoxTransform.get_deltas
-(SURVEY.md C.6), Matcher (C.5), anchors (C.7). Third-party parts "parity unpinned"."""
+(SURVEY.md C.6), Matcher (C.5), anchors (C.7).
+
+Pinned by the reference's own Python (tests/golden/retina_rpn/retina_{labels,losses_*}_xyxy.npz, checked in
+tests/test_retina_rpn_golden_host.py): the foreground / background / ignore encoding with low-quality matches and the empty image, the
+[:, :-1] one-hot, which mask feeds which loss, the EMA normaliser, both box losses and their gradients through the (N, A*K, H, W) ->
+(N, HWA, K) flatten.  Unpinned: the arithmetic of the restated third-party ops (pairwise_iou, Matcher, Box2BoxTransform, focal,
+smooth-L1, GIoU), whose sources exist nowhere."""
 import torch
 
 from . import detection as od

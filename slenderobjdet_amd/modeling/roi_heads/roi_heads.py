@@ -224,7 +224,8 @@ class FastRCNNOutputLayers(nn.Module):
 
 
 def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, nms_thresh, topk_per_image, rotated=False):
-    """d2 fast_rcnn_inference_single_image(_rotated): per-class score threshold, class-aware NMS, top-k."""
+    """d2 fast_rcnn_inference_single_image(_rotated): per-class score threshold, class-aware NMS, top-k.  boxes (R, K*D) class-specific
+    or (R, D) class-agnostic (roi_heads/fast_rcnn.py:78-98: one box per row then serves every class that passes the threshold)."""
     D = 5 if rotated else 4
     valid = torch.isfinite(boxes).all(dim=1) & torch.isfinite(scores).all(dim=1)
     if not bool(valid.all()):
@@ -234,10 +235,11 @@ def fast_rcnn_inference_single_image(boxes, scores, image_shape, score_thresh, n
     BoxT = RotatedBoxes if rotated else Boxes
     b = BoxT(boxes.reshape(-1, D).clone())
     b.clip(image_shape)
-    boxes = b.tensor.view(-1, K, D)
+    num_bbox_reg_classes = boxes.shape[1] // D
+    boxes = b.tensor.view(-1, num_bbox_reg_classes, D)
     mask = scores > score_thresh
     inds = mask.nonzero()
-    boxes, scores = boxes[mask], scores[mask]
+    boxes, scores = (boxes[inds[:, 0], 0] if num_bbox_reg_classes == 1 else boxes[mask]), scores[mask]
     keep = (batched_nms_rotated if rotated else batched_nms)(boxes, scores, inds[:, 1], nms_thresh)
     if topk_per_image >= 0:
         keep = keep[:topk_per_image]

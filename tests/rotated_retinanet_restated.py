@@ -73,7 +73,7 @@ def inference_single_image(level_anchors, level_logits, level_deltas, num_classe
     B, S, C = [], [], []
     for anc, logit, delta in zip(level_anchors, level_logits, level_deltas):
         p = logit.reshape(-1).float().sigmoid()
-        k = min(topk, p.numel())
+        k = min(topk, delta.reshape(-1, 5).shape[0])         # retina_rotated.py:345: capped by the level's ANCHORS, not its anchor x class scores
         prob, idx = p.sort(descending=True, stable=True)
         prob, idx = prob[:k], idx[:k]
         keep = prob > score_thresh

@@ -442,7 +442,7 @@ def test_rcnn_proposals_and_inference_vs_oracle(cuda, rotated):
         lg = [x[..., :A].reshape(N, -1).cpu() for x in logits_l]
         dl = [x[..., :A * D].reshape(N, -1, D).cpu() for x in deltas_l]
         pl = [orc.apply_deltas(d.reshape(-1, D), a.cpu().repeat(N, 1), rpn.box2box_transform.weights).view(N, -1, D) for d, a in zip(dl, anchors_l)]
-        ref = orc.find_top_proposals(pl, lg, imgs.image_sizes, rpn.nms_thresh, 50, 40)
+        ref = orc.find_top_proposals(pl, lg, imgs.image_sizes, rpn.nms_thresh, 50, 40, training=model.training)      # eval mode
         for p, (rb, rs) in zip(proposals, ref):
             assert len(p) == len(rb) and len(rb) > 0
             key = lambda t: set(tuple(round(v, 1) for v in row) for row in t.tolist())

@@ -153,8 +153,7 @@ def test_retinanet_whole_step_losses_and_gradients_vs_oracle(cuda, box_reg):
 
 def test_retinanet_inference_matches_oracle(cuda):
     """retina_rotated.py:296-377: decode + class-aware NMS of the product path's own predictions against the oracle contract."""
-    from oracle import detection as od
-    from oracle import rcnn as orc
+    import retinanet_inference_restated as restated
     from slenderobjdet_amd.data import synthetic_batch
     from slenderobjdet_amd.modeling import build_model
     from slenderobjdet_amd.modeling.anchor_generator import grid_anchors
@@ -178,22 +177,14 @@ def test_retinanet_inference_matches_oracle(cuda):
     anchors_l = grid_anchors(hw, [8, 16, 32, 64, 128], model.anchor_sizes, model.anchor_ratios)
     bounds = list(offs) + [cls_buf.shape[1]]
     for i, r in enumerate(res):
-        B, S, C = [], [], []
-        for l, anc in enumerate(anchors_l):
-            sl = slice(bounds[l], bounds[l + 1])
-            p = cls_buf[i, sl].cpu().reshape(-1).sigmoid()
-            deltas = box_buf[i, sl, :36].cpu().reshape(-1, 4)
-            k = min(model.topk_candidates, deltas.shape[0])
-            prob, idx = p.sort(descending=True)
-            prob, idx = prob[:k], idx[:k]
-            keep = prob > model.score_threshold
-            prob, idx = prob[keep], idx[keep]
-            B.append(orc.apply_deltas(deltas[idx // 80], anc[idx // 80], (1.0, 1.0, 1.0, 1.0))); S.append(prob); C.append(idx % 80)
-        B, S, C = torch.cat(B), torch.cat(S), torch.cat(C)
-        keep = od.batched_nms(B, S, C, model.nms_threshold)[: model.max_detections_per_image]
-        assert len(r) == len(keep) and len(keep) > 0
+        # the contract itself is held to the reference's own output by tests/test_retina_rpn_golden_host.py
+        lv = [slice(bounds[l], bounds[l + 1]) for l in range(len(anchors_l))]
+        rb, _, rc = restated.inference_single_image(anchors_l, [cls_buf[i, s].cpu() for s in lv], [box_buf[i, s, :36].cpu() for s in lv], 80,
+                                                    model.score_threshold, model.topk_candidates, model.nms_threshold,
+                                                    model.max_detections_per_image, (1.0, 1.0, 1.0, 1.0))
+        assert len(r) == len(rb) and len(rb) > 0
         key = lambda b, c: sorted(zip(c.tolist(), [tuple(round(v, 1) for v in x) for x in b.tolist()]))
-        assert key(r.pred_boxes.tensor.cpu(), r.pred_classes.cpu()) == key(B[keep], C[keep])
+        assert key(r.pred_boxes.tensor.cpu(), r.pred_classes.cpu()) == key(rb, rc)
     out = model(data)
     assert len(out) == 2 and "instances" in out[0]
 

@@ -335,7 +335,7 @@ def test_inference_matches_the_restatement(cuda):
         for l, logit in enumerate(lv_logits):
             p = logit.reshape(-1).float().sigmoid()
             prob, idx = p.sort(descending=True, stable=True)
-            k = min(model.topk_candidates, p.numel())
+            k = min(model.topk_candidates, p.numel() // K)          # capped by the level's anchors, as RS.inference_single_image does
             idx = idx[:k][prob[:k] > model.score_threshold]
             ref_anchor.append(torch.div(idx, K, rounding_mode="floor") + sum(rows_per_level[:l]))
         ref_anchor = torch.cat(ref_anchor)
