@@ -211,7 +211,9 @@ int sod_groupnorm_bwd(const void* dy, const void* x, const float* gamma, const f
 int sod_groupnorm_fwd_ml(int nlev, const void* const* x, const float* gamma, const float* beta, void* const* y, float* mean_rstd,
                          int N, const int* hw, int C, int G, float eps, int relu, float* det_ws, long long det_ws_bytes, void* stream);
 /* Second half of sod_groupnorm_fwd_ml for statistics that sod_conv2d_fwd_ml_gnsum gathered: sums_to_mean_rstd holds nlev [N][G][2]
- * blocks of (sum, sum of squares) on entry and (mean, rstd) - what the backward pass takes - on return; y = [relu](norm(x)). */
+ * blocks of (sum, sum of squares) on entry and (mean, rstd) - what the backward pass takes - on return; y = [relu](norm(x)).
+ * These are plain sums (no pivot is known before the conv's output exists): the variance E[x^2] - mean^2 loses about
+ * 2^-24 * (1 + mean^2 / var) relative, where sod_groupnorm_fwd_ml, which sums about a per-group pivot, does not. */
 int sod_groupnorm_apply_ml(int nlev, const void* const* x, const float* gamma, const float* beta, void* const* y, float* sums_to_mean_rstd,
                            int N, const int* hw, int C, int G, float eps, int relu, void* stream);
 int sod_groupnorm_bwd_ml(int nlev, const void* const* dy, const void* const* x, const float* gamma, const float* beta,

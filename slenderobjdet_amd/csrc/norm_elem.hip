@@ -16,7 +16,7 @@ namespace {
 // x: (N, HW, C) bf16; thread owns one 8-channel vector column (c8) and strides over pixels.
 struct GnArgs {
   const __bf16* x; const __bf16* dy; const float* gamma; const float* beta;
-  __bf16* y; __bf16* dx; float* stats;      // stats[N][G][2] : (sum,sumsq) then (mean,rstd)
+  __bf16* y; __bf16* dx; float* stats;      // stats[N][G][2] : (sum,sumsq) of x - gn_pivot, then (mean,rstd)
   float* red;                               // bwd: red[N][G][2] = (sum dy*g, sum dy*g*xhat)
   float* dgamma; float* dbeta;
   float* dxsum;                             // optional: per-channel sum of dx (= bias gradient of the producing conv)
@@ -32,6 +32,20 @@ struct GnArgs {
   float* part_dx;    // [gridDim.x][N][C]        per-channel sum of dx
 };
 
+// The statistics are sums of x - pivot and (x - pivot)^2, the pivot being the mean of the group's first 8 channels at the image's first
+// pixel: var = E[(x - pivot)^2] - E[x - pivot]^2 then cancels like a group of mean/std below 1 whatever the group's own mean is.  (Sums
+// of x and x^2 themselves lost rstd 2.6e-5 relative, and dgamma as much, at mean/std 16 on 2 x 300 x 256, against 3e-7 at mean/std 0 -
+// tests/test_gpu_groupnorm.py.)  The pivot is rounded to bf16: the difference of two bf16 values is exact in fp32 and short, so the
+// partial sums stay exact or nearly so, as sums of bf16 values and of their squares are - a pivot of 24 bits made every addend 24 bits
+// long and cost that (rstd 2.6e-6 instead of 3e-7 at mean/std 1, measured).  Every reader forms the pivot with this function.
+__device__ __forceinline__ float gn_pivot(const __bf16* __restrict__ x_img, int g, int cpg) {
+  const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(x_img + g * cpg);
+  float s = 0.f;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) s += (float)v[e];
+  return (float)(__bf16)(s * 0.125f);
+}
+
 __device__ __forceinline__ void gn_stats_body(const GnArgs& a, const int bx) {
   // Block reduction through plain LDS stores: ds_add_f32 runs at 0.33 lanes/clk/CU on gfx950 (tools/micro/lds_atomic.hip), 40x
   // below ds_write/ds_read, and these kernels ended every block with 2-18 of them per thread.
@@ -44,10 +58,11 @@ __device__ __forceinline__ void gn_stats_body(const GnArgs& a, const int bx) {
   int p1 = p0 + a.pix_per_block; if (p1 > a.HW) p1 = a.HW;
   float s = 0.f, ss = 0.f;
   const __bf16* base = a.x + (long long)n * a.img_stride + c8 * 8;
+  const float piv = gn_pivot(a.x + (long long)n * a.img_stride, (c8 * 8) / a.cpg, a.cpg);
   for (int p = p0 + prow; p < p1; p += rows_per_iter) {
     const bf16x8_t v = *reinterpret_cast<const bf16x8_t*>(base + (long long)p * a.C);
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { const float f = (float)v[e]; s += f; ss += f * f; }
+    for (int e = 0; e < 8; ++e) { const float f = (float)v[e] - piv; s += f; ss += f * f; }
   }
   lsum[threadIdx.x * 2] = s;
   lsum[threadIdx.x * 2 + 1] = ss;
@@ -80,6 +95,7 @@ struct GnML {
   float* part_grp; float* part_gb; float* part_dx;
   int n0;
   int rev;     // walk blocks / images last to first (a pass that re-reads what the previous pass just read starts where that one ended)
+  int pivot;   // the sums in `stats` were taken about gn_pivot (gn_stats_kernel); 0: plain sums of x and x^2 (gathered in a conv epilogue)
 };
 
 __device__ __forceinline__ int gn_bx(const GnML& m) { return m.rev ? (int)(gridDim.x - 1 - blockIdx.x) : (int)blockIdx.x; }
@@ -98,16 +114,20 @@ __device__ __forceinline__ int gn_pick(const GnML& m, GnArgs& a) {
   return l;
 }
 
+// (sum, sum of squares) of group i = (n, g) of level L, about the pivot when m.pivot, -> (mean, rstd) in L.stats
+__device__ __forceinline__ void gn_finalize(const GnML& m, const GnLevel& L, int i, float s, float ss) {
+  const int n = i / m.G, g = i - n * m.G;
+  const float piv = m.pivot ? gn_pivot(L.x + (long long)n * L.img_stride, g, m.cpg) : 0.f;
+  const float dm = s * L.inv_m;
+  const float var = fmaxf(ss * L.inv_m - dm * dm, 0.f);
+  L.stats[i * 2] = piv + dm;
+  L.stats[i * 2 + 1] = rsqrtf(var + m.eps);
+}
+
 __global__ void gn_finalize_stats_kernel(const GnML m) {
   const GnLevel& L = m.lev[blockIdx.y];
   const int i = blockIdx.x * 256 + threadIdx.x;
-  if (i < m.N * m.G) {
-    const float mean = L.stats[i * 2] * L.inv_m;
-    float var = L.stats[i * 2 + 1] * L.inv_m - mean * mean;
-    var = fmaxf(var, 0.f);
-    L.stats[i * 2] = mean;
-    L.stats[i * 2 + 1] = rsqrtf(var + m.eps);
-  }
+  if (i < m.N * m.G) gn_finalize(m, L, i, L.stats[i * 2], L.stats[i * 2 + 1]);
 }
 
 __device__ __forceinline__ void gn_apply_body(const GnArgs& a, const int bx) {
@@ -328,13 +348,10 @@ __global__ void gn_det_group_kernel(const GnML m, int finalize) {
     const float* src = m.part_grp + (((size_t)b * m.N + n) * c8n + (size_t)g * vpg) * 2;
     for (int v = 0; v < vpg; ++v) { s0 += src[v * 2]; s1 += src[v * 2 + 1]; }
   }
-  float* dst = (finalize ? L.stats : L.red) + (size_t)i * 2;
   if (finalize) {
-    const float mean = s0 * L.inv_m;
-    const float var = fmaxf(s1 * L.inv_m - mean * mean, 0.f);
-    dst[0] = mean; dst[1] = rsqrtf(var + m.eps);
+    gn_finalize(m, L, i, s0, s1);
   } else {
-    dst[0] = s0; dst[1] = s1;
+    L.red[(size_t)i * 2] = s0; L.red[(size_t)i * 2 + 1] = s1;
   }
 }
 
@@ -920,7 +937,7 @@ extern "C" int sod_groupnorm_fwd_ml(int nlev, const void* const* x, const float*
   GnML m{};
   const int gx = gn_fill(m, nlev, hw, N, C, G, eps, relu, nullptr);
   if (gx <= 0) return gx ? gx : SOD_EARG;
-  m.gamma = gamma; m.beta = beta;
+  m.gamma = gamma; m.beta = beta; m.pivot = 1;
   for (int l = 0; l < nlev; ++l) {
     if (!x[l] || !y[l]) return SOD_EARG;
     m.lev[l].x = (const __bf16*)x[l]; m.lev[l].y = (__bf16*)y[l]; m.lev[l].stats = mean_rstd + (size_t)l * N * G * 2;
