@@ -638,6 +638,30 @@ int sod_fastrcnn_box_loss_fwd(const float* pred, const int* gt_classes, const fl
 int sod_fastrcnn_box_loss_bwd(const float* pred, const int* gt_classes, const float* gt_deltas, int R, int K, int box_dim, int ld,
                               float beta, const float* grad_scale, float scale_mul, float* dpred, void* stream);
 
+/* The R-CNN heads' BBOX_REG_LOSS_TYPE "giou", "rotated_iou" and "rotated_giou" (csrc/rows_box_loss.hip; detectron2
+ * FastRCNNOutputLayers.box_reg_loss and RPN.losses with a non-smooth-L1 loss type): the fused decode + box loss over R rows.  Row i
+ * regresses from src[i] towards gt[i] (both (R, D)); its deltas are D columns of row i of pred (R, ld) fp32.
+ *   row_form SOD_ROWS_FRCNN: labels int32 (R); foreground = 0 <= label < K; the deltas are columns [label * D, label * D + D), K * D <= ld.
+ *   row_form SOD_ROWS_RPN:   labels int8 (R) in {-1, 0, 1}; foreground = label == 1; the deltas are columns [0, D), D <= ld; K is ignored.
+ *   kind SOD_BOX_LOSS_GIOU (D = 4, ld % 4 == 0): Box2BoxTransform.apply_deltas, then fvcore giou_loss with eps 1e-7.
+ *   kind SOD_BOX_LOSS_ROTATED_IOU / _ROTATED_GIOU (D = 5): Box2BoxTransformRotated.apply_deltas, then 1 - IoU / 1 - IoU + (C - U) / C.
+ * A foreground row runs the code of sod_retina_giou_loss_* / sod_retina_riou_loss_* / sod_retina_rgiou_loss_* at a positive (one
+ * definition: the same numbers give the same bits), with their clamp behaviour: a clamped dw / dh has gradient exactly 0.
+ * fwd: sum_out[0] = the loss summed over the foreground rows, through ws (fixed order: a call is bit-reproducible).
+ * bwd: dpred (R, ld) = grad_scale[0] (device) * scale_mul (host) * d sum / d pred; EVERY element is written (zeros in non-foreground
+ * rows, in the columns of other classes and in the pad columns), so dpred may be uninitialised memory.
+ * R == 0 is legal: sum 0, nothing written.  weights: D positive floats on the host. */
+#define SOD_ROWS_FRCNN 0
+#define SOD_ROWS_RPN 1
+#define SOD_BOX_LOSS_GIOU 0
+#define SOD_BOX_LOSS_ROTATED_IOU 1
+#define SOD_BOX_LOSS_ROTATED_GIOU 2
+int sod_rows_box_loss_fwd(const float* pred, int ld, const void* labels, int row_form, int K, const float* src, const float* gt, int R,
+                          int kind, const float* weights, float scale_clamp, float* sum_out, float* ws, void* stream);
+int sod_rows_box_loss_bwd(const float* pred, int ld, const void* labels, int row_form, int K, const float* src, const float* gt, int R,
+                          int kind, const float* weights, float scale_clamp, const float* grad_scale, float scale_mul, float* dpred,
+                          void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------
  * RepPointsDetector (slender_det/modeling/meta_arch/reppoints/rpd.py:45-798), X = sum of level pixels, point rows pitched by ld.
  * sod_reppoints_dcn_offset: out[r,2k] = scale*pts[r,2k+1] - base_y[k], out[r,2k+1] = scale*pts[r,2k] - base_x[k] (xy->yx flip and

@@ -21,19 +21,9 @@ namespace {
 #include "rotated_iou.h"
 #include "box_transform.h"
 #include "box_pair_loss.h"
+#include "box_loss_policy.h"      // BoxLossArgs, DecodeLossArgs; GiouLoss, RiouLoss, RgiouLoss (shared with rows_box_loss.hip)
 
-struct BoxLossArgs {
-  const float* pred;        // (N, sumHW, pitch) fp32
-  const int* labels;        // (N, R)
-  const float* target;      // (N, R, D): the matched deltas (smooth-L1) or the matched gt boxes (the IoU losses)
-  int N, R, A, pitch, num_classes;
-};
 struct SmoothL1Args : BoxLossArgs { float beta; };
-struct DecodeLossArgs : BoxLossArgs {
-  const float* anchors;     // (R, D)
-  W5 w;
-  float clampv;
-};
 
 template <int D_>
 struct SmoothL1Loss {
@@ -61,56 +51,6 @@ struct SmoothL1Loss {
   }
 };
 
-// retina_rotated.py:236-245; AnchorHead, meta/heads/anchor_head.py:366-374.  The clamp keeps a NaN delta (see ClampForm): the loss is NaN then.
-struct GiouLoss {
-  static constexpr int D = 4;
-  static constexpr bool ROT_LDS = false;
-  using Args = DecodeLossArgs;
-  template <bool BWD>
-  static __device__ __forceinline__ void positive(const Args& a, const float* p, long long r, long long i, P2* pts, float& acc, float* g) {
-    const f32x4_t d = *reinterpret_cast<const f32x4_t*>(p), anc = *reinterpret_cast<const f32x4_t*>(a.anchors + r * 4);
-    const f32x4_t gt = *reinterpret_cast<const f32x4_t*>(a.target + i * 4);
-    float box[4], gb[4];
-    const XyxyDecoded k = xyxy_apply_deltas<CLAMP_KEEPS_NAN>(d, anc, a.w.w, a.clampv, box);
-    acc += giou_pair(box, gt, 1e-7f, BWD ? gb : nullptr);
-    if (BWD) {
-      g[0] = (gb[0] + gb[2]) * k.bw / a.w.w[0];
-      g[1] = (gb[1] + gb[3]) * k.bh / a.w.w[1];
-      g[2] = k.cw ? 0.f : (gb[2] - gb[0]) * 0.5f * k.pw / a.w.w[2];
-      g[3] = k.ch ? 0.f : (gb[3] - gb[1]) * 0.5f * k.ph / a.w.w[3];
-    }
-  }
-};
-
-// The IoU is iou_rotated_lds (the number NMS, the matcher and the evaluator see); a positive whose IoU is 0 has no gradient.
-// HULL: with the hull term of rgiou_pair, which leaves such a positive a gradient.
-template <bool HULL>
-struct RotIouLoss {
-  static constexpr int D = 5;
-  static constexpr bool ROT_LDS = true;
-  using Args = DecodeLossArgs;
-  template <bool BWD>
-  static __device__ __forceinline__ void positive(const Args& a, const float* p, long long r, long long i, P2* pts, float& acc, float* g) {
-    float d[5], s[5], t[5], box[5];
-#pragma unroll
-    for (int e = 0; e < 5; ++e) { d[e] = p[e]; s[e] = a.anchors[r * 5 + e]; t[e] = a.target[i * 5 + e]; }
-    const RotDecoded k = rot_apply_deltas(d, s, a.w.w, a.clampv, box);
-    const float iou = iou_rotated_lds(box, t, pts, 256);
-    float gb[5];
-    if constexpr (HULL) acc += rgiou_pair<BWD>(box, t, iou, gb);
-    else acc += 1.f - iou;
-    if (BWD && (HULL || iou > 0.f)) {
-      if constexpr (!HULL) riou_grad(box, t, iou, gb);
-      g[0] = gb[0] * s[2] / a.w.w[0];
-      g[1] = gb[1] * s[3] / a.w.w[1];
-      g[2] = k.cw ? 0.f : gb[2] * box[2] / a.w.w[2];
-      g[3] = k.ch ? 0.f : gb[3] * box[3] / a.w.w[3];
-      g[4] = gb[4] * 180.f / (SOD_PI * a.w.w[4]);
-    }
-  }
-};
-using RiouLoss = RotIouLoss<false>;
-using RgiouLoss = RotIouLoss<true>;
 
 // T: storage type of the delta gradient (bf16 product path, float in the fp32 validation mode)
 template <class Loss, bool BWD, typename T>

@@ -1894,6 +1894,46 @@ def fastrcnn_box_loss_bwd(pred, gt_classes, gt_deltas, K, beta, grad_scale, scal
     return d
 
 
+# The R-CNN heads' IoU box losses over rows (csrc/rows_box_loss.hip).  loss_type: the config's BBOX_REG_LOSS_TYPE; rows: "frcnn" (int32
+# class labels, class-specific delta columns, K classes) or "rpn" (int8 labels in {-1, 0, 1}, D columns).
+ROWS_BOX_LOSS_KINDS = {"giou": (0, 4), "rotated_iou": (1, 5), "rotated_giou": (2, 5)}
+_ROWS_FORMS = {"frcnn": (0, torch.int32), "rpn": (1, torch.int8)}
+
+
+def _rows_box_loss_args(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp):
+    """Checks the buffers against each other - the kernel indexes by R, ld, K and D alone - and returns the C arguments up to scale_clamp.
+    The keep-alive of the weights' ctypes array is the returned list itself."""
+    if loss_type not in ROWS_BOX_LOSS_KINDS or rows not in _ROWS_FORMS:
+        raise _C.SlenderHipError(f"rows_box_loss: loss_type {loss_type!r} must be one of {sorted(ROWS_BOX_LOSS_KINDS)}, rows {rows!r} 'frcnn' or 'rpn'")
+    (kind, D), (form, ldt) = ROWS_BOX_LOSS_KINDS[loss_type], _ROWS_FORMS[rows]
+    _chk(pred, torch.float32, "pred"); _chk(labels, ldt, "labels"); _chk(src, torch.float32, "src"); _chk(gt, torch.float32, "gt")
+    K = int(K) if rows == "frcnn" else 1
+    if not (pred.dim() == 2 and labels.numel() == pred.shape[0] and tuple(src.shape) == (pred.shape[0], D) and src.shape == gt.shape
+            and K > 0 and K * D <= pred.shape[1] and len(weights) == D):
+        raise _C.SlenderHipError(f"rows_box_loss ({loss_type}, {rows}): pred (R, ld >= K * {D}), labels (R), src and gt (R, {D}), {D} weights")
+    R, ld = pred.shape
+    return [ptr(pred), ld, ptr(labels), form, K, ptr(src), ptr(gt), R, kind, _float_arr(weights), float(scale_clamp)]
+
+
+def rows_box_loss_fwd(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp):
+    """The loss summed over the foreground rows, (1,) fp32."""
+    args = _rows_box_loss_args(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp)
+    s = _sum1(pred.device)
+    call("sod_rows_box_loss_fwd", *args, ptr(s), ptr(reduce_ws(pred.device)), stream_ptr())
+    return s
+
+
+def rows_box_loss_bwd(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp, grad_scale, scale_mul, out=None):
+    """grad_scale[0] * scale_mul * d sum / d pred, (R, ld) fp32 with every element written (into ``out`` when given)."""
+    args = _rows_box_loss_args(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp)
+    _chk(grad_scale, torch.float32, "grad_scale"); _chk(out, torch.float32, "out")
+    if out is not None and out.shape != pred.shape:
+        raise _C.SlenderHipError("rows_box_loss_bwd: out must have pred's shape")
+    d = torch.empty_like(pred) if out is None else out
+    call("sod_rows_box_loss_bwd", *args, ptr(grad_scale), float(scale_mul), ptr(d), stream_ptr())
+    return d
+
+
 def bce_logits_soft_fwd(logits, targets, labels, bg_label):
     """BCE-with-logits (sum) with float targets over the rows whose int32 label is a foreground class."""
     _chk(logits, torch.float32, "logits"); _chk(targets, torch.float32, "targets"); _chk(labels, torch.int32, "labels")

@@ -24,7 +24,7 @@ from ...layers.nn import ConvML, _arena_of
 from ...structures import Boxes, Instances, RotatedBoxes
 from ...utils.registry import Registry
 from ..anchor_generator import build_anchor_generator
-from ..box_regression import Box2BoxTransform, Box2BoxTransformRotated
+from ..box_regression import BOX_REG_LOSS_TYPES, Box2BoxTransform, Box2BoxTransformRotated
 
 PROPOSAL_GENERATOR_REGISTRY = Registry("PROPOSAL_GENERATOR")
 RPN_HEAD_REGISTRY = Registry("RPN_HEAD")
@@ -160,7 +160,9 @@ class _RpnLossFn(torch.autograd.Function):
     the sampled anchors (<= BATCH_SIZE_PER_IMAGE per image; everything else is label -1): the rows of those anchors are gathered from
     the head outputs (sod_rpn_gather_sampled), the two loss kernels see (N, S) / (N, S, D) tensors, and backward scatters the row
     gradients into zero tensors of the head outputs' shapes - instead of compacting, labelling and differentiating all ~1.6 M anchors
-    of an image (the dense formulation moved ~3 GB per step at batch 16)."""
+    of an image (the dense formulation moved ~3 GB per step at batch 16).  ``deltas_s``: the sampled anchors' target deltas (N, S, D)
+    (smooth-L1) or, for the IoU losses, the pair (sampled anchors, their matched gt boxes), each (N, S, D): the loss kernel decodes the
+    gathered delta rows against the anchors."""
 
     @staticmethod
     def forward(ctx, rpn, idx, labels_s, deltas_s, *outs):
@@ -171,20 +173,33 @@ class _RpnLossFn(torch.autograd.Function):
         N = logits.shape[0]
         norm = float(rpn.batch_size_per_image * N)
         s_cls = HF.bce_logits_loss_fwd(logits, labels_s)
-        s_loc = HF.rpn_loc_loss_fwd(deltas, deltas_s, labels_s, rpn.smooth_l1_beta)
+        ctx.iou_loss = rpn.box_reg_loss_type != "smooth_l1"
+        if ctx.iou_loss:
+            t = rpn.box2box_transform
+            src_s, gt_s = (x.view(-1, D) for x in deltas_s)
+            s_loc = HF.rows_box_loss_fwd(rpn.box_reg_loss_type, "rpn", deltas.view(-1, D), labels_s, 1, src_s, gt_s, t.weights, t.scale_clamp)
+            targets = (src_s, gt_s)
+        else:
+            s_loc = HF.rpn_loc_loss_fwd(deltas, deltas_s, labels_s, rpn.smooth_l1_beta)
+            targets = (deltas_s,)
         ctx.rpn, ctx.nl, ctx.norm = rpn, nl, norm
         ctx.shapes = [tuple(o.shape) for o in outs]
-        ctx.save_for_backward(logits, deltas, labels_s, deltas_s, idx)
+        ctx.save_for_backward(logits, deltas, labels_s, idx, *targets)
         return torch.cat([s_cls, s_loc]) / norm
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g2):
         rpn, nl = ctx.rpn, ctx.nl
-        logits, deltas, labels_s, deltas_s, idx = ctx.saved_tensors
+        logits, deltas, labels_s, idx, *targets = ctx.saved_tensors
         g2 = g2.contiguous().float()
         dl = HF.bce_logits_loss_bwd(logits, labels_s, g2[0:1], 1.0 / ctx.norm)
-        dd = HF.rpn_loc_loss_bwd(deltas, deltas_s, labels_s, rpn.smooth_l1_beta, g2[1:2], 1.0 / ctx.norm)
+        if ctx.iou_loss:
+            t, D = rpn.box2box_transform, rpn.head.box_dim
+            dd = HF.rows_box_loss_bwd(rpn.box_reg_loss_type, "rpn", deltas.view(-1, D), labels_s, 1, targets[0], targets[1], t.weights,
+                                      t.scale_clamp, g2[1:2], 1.0 / ctx.norm).view(deltas.shape)
+        else:
+            dd = HF.rpn_loc_loss_bwd(deltas, targets[0], labels_s, rpn.smooth_l1_beta, g2[1:2], 1.0 / ctx.norm)
         g_log, g_del = HF.rpn_scatter_sampled(ctx.shapes[:nl], ctx.shapes[nl:], idx, rpn.head.num_anchors, rpn.head.box_dim, dl, dd)
         return (None, None, None, None, *g_log, *g_del)
 
@@ -235,12 +250,16 @@ class RPN(nn.Module):
         self.iou_thresholds, self.iou_labels = list(r.IOU_THRESHOLDS), list(r.IOU_LABELS)
         self.batch_size_per_image, self.positive_fraction = r.BATCH_SIZE_PER_IMAGE, r.POSITIVE_FRACTION
         self.smooth_l1_beta = r.SMOOTH_L1_BETA
+        self.box_reg_loss_type = r.BBOX_REG_LOSS_TYPE
+        if self.box_reg_loss_type not in BOX_REG_LOSS_TYPES[self.box_dim]:
+            raise ValueError(f"{type(self).__name__}: MODEL.RPN.BBOX_REG_LOSS_TYPE must be one of {BOX_REG_LOSS_TYPES[self.box_dim]} "
+                             f"for {self.box_dim}-parameter boxes, got {self.box_reg_loss_type!r}")
         self.loss_weight = {"loss_rpn_cls": r.LOSS_WEIGHT, "loss_rpn_loc": r.BBOX_REG_LOSS_WEIGHT * r.LOSS_WEIGHT}
         self.pre_nms_topk = {True: r.PRE_NMS_TOPK_TRAIN, False: r.PRE_NMS_TOPK_TEST}
         self.post_nms_topk = {True: r.POST_NMS_TOPK_TRAIN, False: r.POST_NMS_TOPK_TEST}
         self.nms_thresh = r.NMS_THRESH
         self.min_box_size = float(cfg.MODEL.PROPOSAL_GENERATOR.MIN_SIZE)
-        self.last_targets = None
+        self.last_targets = self.last_sampled = None
 
     # ------------------------------------------------------------------ helpers
     def _box_type(self):
@@ -265,8 +284,9 @@ class RPN(nn.Module):
         return labels, matches, idx
 
     @torch.no_grad()
-    def sampled_targets(self, anchors, gt_instances, labels, matches, idx):
-        """For the sampled anchors idx (N, S) (-1 padded): their labels (N, S) int8 and regression targets (N, S, D)."""
+    def sampled_targets(self, anchors, gt_instances, labels, matches, idx, want_boxes=False):
+        """For the sampled anchors idx (N, S) (-1 padded): their labels (N, S) int8 and regression targets (N, S, D).  ``want_boxes``: in
+        place of the target deltas, the pair (sampled anchors, their matched gt boxes), each (N, S, D) - what the IoU losses compare."""
         S = self.batch_size_per_image
         safe = idx.clamp(min=0).long()
         labels_s = torch.where(idx >= 0, torch.gather(labels, 1, safe), torch.full_like(safe, -1, dtype=torch.int8)).contiguous()
@@ -277,12 +297,15 @@ class RPN(nn.Module):
             off.append(off[-1] + c)
         D = anchors.shape[1]
         if off[-1] == 0:
-            return idx, labels_s, torch.zeros((len(gts), S, D), dtype=torch.float32, device=anchors.device), torch.zeros((0, D), device=anchors.device), off
+            zeros = torch.zeros((len(gts), S, D), dtype=torch.float32, device=anchors.device)      # no positives: never read
+            return idx, labels_s, ((zeros, zeros) if want_boxes else zeros), torch.zeros((0, D), device=anchors.device), off
         gt_cat = torch.cat(gts).contiguous()
         base = torch.tensor(off[:-1], dtype=torch.int64, device=anchors.device)[:, None]
         m_s = torch.gather(matches, 1, safe).long()
         # images without boxes have no positives: their rows point at box 0 of the batch and are never read (label != 1)
         tgt = gt_cat[(base + m_s).clamp(max=off[-1] - 1).reshape(-1)]
+        if want_boxes:
+            return idx, labels_s, (anchors[safe.reshape(-1)].view(len(gts), S, D), tgt.view(len(gts), S, D)), gt_cat, off
         deltas_s = self.box2box_transform.get_deltas(anchors[safe.reshape(-1)].contiguous(), tgt.contiguous()).view(len(gts), S, D)
         return idx, labels_s, deltas_s, gt_cat, off
 
@@ -339,8 +362,11 @@ class RPN(nn.Module):
         if self.training:
             anchors = torch.cat(anchors_l).contiguous()
             gt_labels, matches, idx = self.label_and_sample_anchors(anchors, gt_instances)
-            idx, labels_s, deltas_s, gt_cat, gt_off = self.sampled_targets(anchors, gt_instances, gt_labels, matches, idx)
+            idx, labels_s, deltas_s, gt_cat, gt_off = self.sampled_targets(anchors, gt_instances, gt_labels, matches, idx,
+                                                                           want_boxes=self.box_reg_loss_type != "smooth_l1")
             self.last_targets = _RpnTargets(self, anchors, gt_labels, matches, gt_cat, gt_off)
+            # what the IoU losses read (tests compare against it); smooth-L1 keeps nothing beyond what it kept before
+            self.last_sampled = (idx, labels_s, deltas_s) if self.box_reg_loss_type != "smooth_l1" else None
             out = _RpnLossFn.apply(self, idx, labels_s, deltas_s, *logits_l, *deltas_l)
             losses = {"loss_rpn_cls": out[0] * self.loss_weight["loss_rpn_cls"], "loss_rpn_loc": out[1] * self.loss_weight["loss_rpn_loc"]}
         proposals = self.predict_proposals(anchors_l, [x.detach() for x in logits_l], [x.detach() for x in deltas_l], images.image_sizes)

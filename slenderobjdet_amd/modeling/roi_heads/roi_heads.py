@@ -23,7 +23,7 @@ from ...layers.nn import HipConv2d
 from ...structures import Boxes, Instances, RotatedBoxes
 from ...utils.registry import Registry
 from ...layers import nn as _nn
-from ..box_regression import Box2BoxTransform, Box2BoxTransformRotated
+from ..box_regression import BOX_REG_LOSS_TYPES, Box2BoxTransform, Box2BoxTransformRotated
 
 ROI_HEADS_REGISTRY = Registry("ROI_HEADS")
 ROI_BOX_HEAD_REGISTRY = Registry("ROI_BOX_HEAD")
@@ -148,27 +148,41 @@ class FastRCNNConvFCHead(nn.Module):
 
 
 class _FastRcnnLossFn(torch.autograd.Function):
+    """[loss_cls, loss_box_reg] over the sampled rows, both divided by their number.  ``box_target``: the matched deltas (smooth-L1) or,
+    for the IoU losses, the matched gt boxes - those decode the foreground rows' deltas of the gt class against ``boxes`` (the proposals;
+    None with smooth-L1, which then saves exactly the tensors it saved before there was a choice) inside the loss kernel, so get_deltas
+    is never run."""
+
     @staticmethod
-    def forward(ctx, pred, scores, deltas, gt_classes, gt_deltas):
+    def forward(ctx, pred, scores, deltas, gt_classes, box_target, boxes=None):
         R = scores.shape[0]
         s2, d2 = scores.view(R, -1), deltas.view(R, -1)
         K, D = pred.num_classes, pred.box_dim
         s_cls = HF.softmax_ce_fwd(s2, gt_classes, K + 1)
-        s_box = HF.fastrcnn_box_loss_fwd(d2, gt_classes, gt_deltas, K, pred.smooth_l1_beta)
+        if pred.box_reg_loss_type == "smooth_l1":
+            s_box = HF.fastrcnn_box_loss_fwd(d2, gt_classes, box_target, K, pred.smooth_l1_beta)
+        else:
+            t = pred.box2box_transform
+            s_box = HF.rows_box_loss_fwd(pred.box_reg_loss_type, "frcnn", d2, gt_classes, K, boxes, box_target, t.weights, t.scale_clamp)
         ctx.pred = pred
-        ctx.save_for_backward(s2, d2, gt_classes, gt_deltas)
+        ctx.save_for_backward(s2, d2, gt_classes, box_target, *(() if boxes is None else (boxes,)))
         return torch.cat([s_cls, s_box]) / max(R, 1)
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g2):
         pred = ctx.pred
-        s2, d2, gt_classes, gt_deltas = ctx.saved_tensors
+        s2, d2, gt_classes, box_target, *boxes = ctx.saved_tensors
         R = s2.shape[0]
         g2 = g2.contiguous().float()
         ds = HF.softmax_ce_bwd(s2, gt_classes, pred.num_classes + 1, g2[0:1], 1.0 / max(R, 1))
-        dd = HF.fastrcnn_box_loss_bwd(d2, gt_classes, gt_deltas, pred.num_classes, pred.smooth_l1_beta, g2[1:2], 1.0 / max(R, 1))
-        return None, ds.view(R, 1, 1, -1), dd.view(R, 1, 1, -1), None, None
+        if pred.box_reg_loss_type == "smooth_l1":
+            dd = HF.fastrcnn_box_loss_bwd(d2, gt_classes, box_target, pred.num_classes, pred.smooth_l1_beta, g2[1:2], 1.0 / max(R, 1))
+        else:
+            t = pred.box2box_transform
+            dd = HF.rows_box_loss_bwd(pred.box_reg_loss_type, "frcnn", d2, gt_classes, pred.num_classes, boxes[0], box_target, t.weights,
+                                      t.scale_clamp, g2[1:2], 1.0 / max(R, 1))
+        return None, ds.view(R, 1, 1, -1), dd.view(R, 1, 1, -1), None, None, None
 
 
 class FastRCNNOutputLayers(nn.Module):
@@ -180,6 +194,11 @@ class FastRCNNOutputLayers(nn.Module):
         if cfg.MODEL.ROI_BOX_HEAD.CLS_AGNOSTIC_BBOX_REG:
             raise NotImplementedError("CLS_AGNOSTIC_BBOX_REG is not built")
         self.smooth_l1_beta = cfg.MODEL.ROI_BOX_HEAD.SMOOTH_L1_BETA
+        self.box_reg_loss_type = cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE
+        if self.box_reg_loss_type not in BOX_REG_LOSS_TYPES[self.box_dim]:
+            raise ValueError(f"{cfg.MODEL.ROI_HEADS.NAME}: MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE must be one of {BOX_REG_LOSS_TYPES[self.box_dim]} "
+                             f"for {self.box_dim}-parameter boxes, got {self.box_reg_loss_type!r}")
+        self.box_reg_loss_weight = float(cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_WEIGHT)
         self.test_score_thresh, self.test_nms_thresh = cfg.MODEL.ROI_HEADS.SCORE_THRESH_TEST, cfg.MODEL.ROI_HEADS.NMS_THRESH_TEST
         self.test_topk_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.cls_pad, self.box_out = _ceil8(self.num_classes + 1), _ceil8(self.num_classes * self.box_dim)
@@ -201,10 +220,16 @@ class FastRCNNOutputLayers(nn.Module):
         gt_classes = torch.cat([p.gt_classes for p in proposals]).to(torch.int32).contiguous()
         boxes = torch.cat([p.proposal_boxes.tensor for p in proposals]).float().contiguous()
         gt_boxes = torch.cat([p.gt_boxes.tensor for p in proposals]).float().contiguous()
-        with torch.no_grad():
-            gt_deltas = self.box2box_transform.get_deltas(boxes, gt_boxes)
-        out = _FastRcnnLossFn.apply(self, scores, deltas, gt_classes, gt_deltas)
-        return {"loss_cls": out[0], "loss_box_reg": out[1]}
+        if self.box_reg_loss_type == "smooth_l1":
+            with torch.no_grad():
+                box_target = self.box2box_transform.get_deltas(boxes, gt_boxes)
+        else:
+            box_target = gt_boxes             # the IoU losses compare decoded boxes: no deltas
+        out = _FastRcnnLossFn.apply(self, scores, deltas, gt_classes, box_target, None if self.box_reg_loss_type == "smooth_l1" else boxes)
+        loss_box_reg = out[1]
+        if self.box_reg_loss_weight != 1.0:   # the default runs no multiply (and keeps its bits)
+            loss_box_reg = loss_box_reg * self.box_reg_loss_weight
+        return {"loss_cls": out[0], "loss_box_reg": loss_box_reg}
 
     @torch.no_grad()
     def inference(self, predictions, proposals):

@@ -1,0 +1,146 @@
+"""The R-CNN heads' box regression losses (MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / MODEL.RPN.BBOX_REG_LOSS_TYPE) on the rotated R-CNN of
+configs/rotated/faster_R_101.yaml at the benchmark's settings (batch 16, 1333 x 800 images, R50-FPN, bf16 product path, synthetic rotated
+batches, bench.train_step with prefetch and the warm-up schedule), one card:
+  * us per call of the row kernels ``sod_rows_box_loss_{fwd,bwd}`` ("rotated_iou", "rotated_giou") beside the smooth-L1 kernels they stand
+    in for, at the step's real row counts: Fast R-CNN rows 16 x 512 = 8 192 of K = 80 classes (ld = 400, a quarter foreground) beside
+    ``sod_fastrcnn_box_loss_*``, RPN rows 16 x 256 = 4 096 (ld = 5, half positive) beside ``sod_rpn_loc_loss_*``; calls issued back to back
+    from Python, device events, warm-up, three alternating windows of --calls calls each;
+  * img/s of the full training step with ``--box-loss`` on both stages (one loss per process: alternate the runs from a script).
+``--root DIR`` imports the package and bench.py from another checkout - the parent commit's tree, whose smooth_l1 step is to be timed in
+alternating runs with this tree's; the kernel part is skipped where that checkout has no row kernels.  Prints the card's shader clock
+with the figures.
+
+    python tools/bench_rcnn_box_loss.py [--box-loss smooth_l1|rotated_iou|rotated_giou] [--steps 20] [--warmup 5] [--calls 50]
+                                        [--skip-kernels] [--skip-step] [--root DIR] [--out FILE]
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--steps", type=int, default=20)
+ap.add_argument("--warmup", type=int, default=5)
+ap.add_argument("--calls", type=int, default=50, help="timed calls per window of the kernel comparison (three windows per entry point)")
+ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou"], default="smooth_l1", help="the loss of both stages in the timed step")
+ap.add_argument("--skip-kernels", action="store_true", help="only the training step")
+ap.add_argument("--skip-step", action="store_true", help="only the kernel comparison")
+ap.add_argument("--root", default=None, help="checkout to import slenderobjdet_amd and bench from (default: this one)")
+ap.add_argument("--out", default=None, help="also write the JSON result to this file")
+args = ap.parse_args()
+
+ROOT = os.path.abspath(args.root) if args.root else os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from bench import damp_residual_branches, device_fingerprint, make_cfg, train_step  # noqa: E402
+from slenderobjdet_amd.data import SyntheticCocoBatches  # noqa: E402
+from slenderobjdet_amd.layers import functional as HF  # noqa: E402
+from slenderobjdet_amd.modeling import build_model  # noqa: E402
+from slenderobjdet_amd.solver import build_lr_scheduler, build_optimizer  # noqa: E402
+
+if not torch.cuda.is_available():
+    raise SystemExit("bench_rcnn_box_loss: needs a GPU (there is no CPU path to time)")
+dev = torch.device("cuda:0")
+torch.cuda.set_device(0)
+N, H, W, K, D = 16, 800, 1333, 80, 5
+W_ROI, W_RPN, CLAMP = (10.0, 10.0, 5.0, 5.0, 1.0), (1.0, 1.0, 1.0, 1.0, 1.0), 4.135166556742356
+out = {"root": ROOT, "box_loss": args.box_loss, "device": device_fingerprint(0)}
+
+
+def window(fn, reps):
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(reps):
+        fn()
+    e.record(); torch.cuda.synchronize()
+    return s.elapsed_time(e) / reps * 1e3        # us per call
+
+
+# ---------------------------------------------------------------------------------------------- kernels
+if not args.skip_kernels and hasattr(HF, "rows_box_loss_fwd"):
+    g = torch.Generator().manual_seed(1)
+
+    def boxes(n):
+        return torch.cat([16 + 1200 * torch.rand(n, 2, generator=g), 8 + 200 * torch.rand(n, 1, generator=g), 4 + 40 * torch.rand(n, 1, generator=g),
+                          360 * torch.rand(n, 1, generator=g) - 180], 1)
+
+    def near(b):      # a box a proposal / an anchor is matched with: overlapping, not equal
+        return b + torch.cat([4 * torch.randn(len(b), 2, generator=g), 6 * torch.randn(len(b), 2, generator=g).abs(), 8 * torch.randn(len(b), 1, generator=g)], 1)
+
+    one = torch.ones(1, device=dev)
+    R1, ld = N * 512, (K * D + 7) // 8 * 8
+    src1 = boxes(R1); gt1 = near(src1)
+    cls = torch.where(torch.rand(R1, generator=g) < 0.25, torch.randint(0, K, (R1,), generator=g), torch.full((R1,), K)).to(torch.int32)
+    pred1 = (0.1 * torch.randn(R1, ld, generator=g)).to(dev)
+    src1, gt1, cls = src1.to(dev), gt1.to(dev), cls.to(dev)
+    dl1 = HF.box2box_get_deltas(src1, gt1, W_ROI)
+    R2 = N * 256
+    src2 = boxes(R2); gt2 = near(src2)
+    lab8 = torch.where(torch.rand(R2, generator=g) < 0.5, 1, 0).to(torch.int8).to(dev)
+    pred2 = (0.1 * torch.randn(R2, D, generator=g)).to(dev)
+    src2, gt2 = src2.to(dev), gt2.to(dev)
+    dl2 = HF.box2box_get_deltas(src2, gt2, W_RPN)
+    entries = {
+        "fastrcnn_box_loss_fwd (smooth_l1)": lambda: HF.fastrcnn_box_loss_fwd(pred1, cls, dl1, K, 0.0),
+        "fastrcnn_box_loss_bwd (smooth_l1)": lambda: HF.fastrcnn_box_loss_bwd(pred1, cls, dl1, K, 0.0, one, 1.0 / R1),
+        "rpn_loc_loss_fwd (smooth_l1)": lambda: HF.rpn_loc_loss_fwd(pred2, dl2, lab8, 0.0),
+        "rpn_loc_loss_bwd (smooth_l1)": lambda: HF.rpn_loc_loss_bwd(pred2, dl2, lab8, 0.0, one, 1.0 / R2),
+    }
+    for kind in ("rotated_iou", "rotated_giou"):
+        entries[f"rows_box_loss_fwd frcnn ({kind})"] = lambda kind=kind: HF.rows_box_loss_fwd(kind, "frcnn", pred1, cls, K, src1, gt1, W_ROI, CLAMP)
+        entries[f"rows_box_loss_bwd frcnn ({kind})"] = lambda kind=kind: HF.rows_box_loss_bwd(kind, "frcnn", pred1, cls, K, src1, gt1, W_ROI, CLAMP, one, 1.0 / R1)
+        entries[f"rows_box_loss_fwd rpn ({kind})"] = lambda kind=kind: HF.rows_box_loss_fwd(kind, "rpn", pred2, lab8, 1, src2, gt2, W_RPN, CLAMP)
+        entries[f"rows_box_loss_bwd rpn ({kind})"] = lambda kind=kind: HF.rows_box_loss_bwd(kind, "rpn", pred2, lab8, 1, src2, gt2, W_RPN, CLAMP, one, 1.0 / R2)
+    for fn in entries.values():
+        for _ in range(3):
+            fn()
+    torch.cuda.synchronize()
+    times = {k: [] for k in entries}
+    for _ in range(3):                                # the entry points alternate: three windows each
+        for k, fn in entries.items():
+            times[k].append(window(fn, args.calls))
+    out["kernels"] = {"frcnn_rows": R1, "frcnn_foreground": int(((cls >= 0) & (cls < K)).sum()), "ld": ld, "rpn_rows": R2,
+                      "rpn_positive": int((lab8 == 1).sum()), "calls_per_window": args.calls,
+                      "us_per_call": {k: [round(t, 1) for t in v] for k, v in times.items()}}
+    print(f"Fast R-CNN rows {R1} x {ld} ({out['kernels']['frcnn_foreground']} foreground), RPN rows {R2} x {D} ({out['kernels']['rpn_positive']} positive); "
+          f"us per call, three windows of {args.calls} calls:", flush=True)
+    for k, v in times.items():
+        print(f"  {k:48s} {sum(v) / len(v):8.1f}  {[round(t, 1) for t in v]}", flush=True)
+
+# ---------------------------------------------------------------------------------------------- training step
+if not args.skip_step:
+    cfg = make_cfg(50, "rrcnn")
+    cfg.MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE = args.box_loss
+    cfg.MODEL.RPN.BBOX_REG_LOSS_TYPE = args.box_loss
+    torch.manual_seed(1)
+    model = build_model(cfg)
+    model.train()
+    damp_residual_branches(model)      # random-init R50 without a checkpoint overflows the un-normalised heads (bench.py)
+    opt = build_optimizer(cfg, model)
+    sched = build_lr_scheduler(cfg, opt)
+    loader = SyntheticCocoBatches(N, H, W, rank=0, device=dev, pool=2, rotated=True)
+    cur = next(loader)
+    for _ in range(args.warmup):
+        nxt = next(loader)
+        train_step(model, opt, cur, nxt, sched)
+        cur = nxt
+    torch.cuda.synchronize()
+    s, e = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    s.record()
+    for _ in range(args.steps):
+        nxt = next(loader)
+        total = train_step(model, opt, cur, nxt, sched)
+        cur = nxt
+    e.record(); torch.cuda.synchronize()
+    ips = N * args.steps / (s.elapsed_time(e) * 1e-3)
+    total = total.detach()
+    out["GeneralizedRCNN+RRPN+RROIHeads"] = {"img_per_s": round(ips, 1), "steps": args.steps, "warmup": args.warmup, "last_total_loss": round(float(total), 4)}
+    print(f"GeneralizedRCNN+RRPN+RROIHeads, {args.box_loss}: {ips:7.1f} img/s over {args.steps} steps (last total loss {float(total):.4f})", flush=True)
+out["device_after"] = device_fingerprint(0, clocks_only=True)
+line = json.dumps(out)
+print(line)
+if args.out:
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        f.write(line + "\n")
