@@ -577,7 +577,7 @@ int sod_f32_to_bf16(const float* x, void* y, long long n, void* stream);
  * sod_retina_box_loss_* = smooth_l1_loss(pred_deltas[pos], gt_deltas[pos], beta, "sum") (:229) on the pitched prediction buffer
  * (anchor a of pixel p at p*pitch + a*4) + the EMA loss normaliser (:210-214) kept on the device:
  * normalizer <- momentum*normalizer + (1-momentum)*max(num_pos,1); sums2 = {loss sum, num_pos}.
- * The contract of all five fused box losses (csrc/retina_box_loss.hip: sod_retina_{box,box5,giou,riou,rgiou}_loss_*, D = 4, 5, 4, 5, 5 deltas per
+ * The contract of all six fused box losses (csrc/retina_box_loss.hip: sod_retina_{box,box5,giou,riou,rgiou,rkld}_loss_*, D = 4, 5, 4, 5, 5, 5 deltas per
  * anchor), said once: pred and dpred are (N, R / A, pitch) with pitch >= A*D, gt_labels (N, R), the target (N, R, D); the sizes are not
  * checked beyond that (the caller's job); positives are 0 <= label != num_classes.  bwd writes EVERY element of every pixel's pitch-wide
  * row of dpred (bf16, or fp32 for *_bwd_f32): grad_num[0] / grad_den[0] * d sum / d pred in the D columns of a positive, exact zeros in
@@ -638,14 +638,15 @@ int sod_fastrcnn_box_loss_fwd(const float* pred, const int* gt_classes, const fl
 int sod_fastrcnn_box_loss_bwd(const float* pred, const int* gt_classes, const float* gt_deltas, int R, int K, int box_dim, int ld,
                               float beta, const float* grad_scale, float scale_mul, float* dpred, void* stream);
 
-/* The R-CNN heads' BBOX_REG_LOSS_TYPE "giou", "rotated_iou" and "rotated_giou" (csrc/rows_box_loss.hip; detectron2
+/* The R-CNN heads' BBOX_REG_LOSS_TYPE "giou", "rotated_iou", "rotated_giou" and "rotated_kld" (csrc/rows_box_loss.hip; detectron2
  * FastRCNNOutputLayers.box_reg_loss and RPN.losses with a non-smooth-L1 loss type): the fused decode + box loss over R rows.  Row i
  * regresses from src[i] towards gt[i] (both (R, D)); its deltas are D columns of row i of pred (R, ld) fp32.
  *   row_form SOD_ROWS_FRCNN: labels int32 (R); foreground = 0 <= label < K; the deltas are columns [label * D, label * D + D), K * D <= ld.
  *   row_form SOD_ROWS_RPN:   labels int8 (R) in {-1, 0, 1}; foreground = label == 1; the deltas are columns [0, D), D <= ld; K is ignored.
  *   kind SOD_BOX_LOSS_GIOU (D = 4, ld % 4 == 0): Box2BoxTransform.apply_deltas, then fvcore giou_loss with eps 1e-7.
  *   kind SOD_BOX_LOSS_ROTATED_IOU / _ROTATED_GIOU (D = 5): Box2BoxTransformRotated.apply_deltas, then 1 - IoU / 1 - IoU + (C - U) / C.
- * A foreground row runs the code of sod_retina_giou_loss_* / sod_retina_riou_loss_* / sod_retina_rgiou_loss_* at a positive (one
+ *   kind SOD_BOX_LOSS_ROTATED_KLD (D = 5): the same decode, then the Gaussian KL-divergence loss of sod_rotated_kld_loss (no LDS beyond the reduction's).
+ * A foreground row runs the code of sod_retina_giou_loss_* / sod_retina_riou_loss_* / sod_retina_rgiou_loss_* / sod_retina_rkld_loss_* at a positive (one
  * definition: the same numbers give the same bits), with their clamp behaviour: a clamped dw / dh has gradient exactly 0.
  * fwd: sum_out[0] = the loss summed over the foreground rows, through ws (fixed order: a call is bit-reproducible).
  * bwd: dpred (R, ld) = grad_scale[0] (device) * scale_mul (host) * d sum / d pred; EVERY element is written (zeros in non-foreground
@@ -656,6 +657,7 @@ int sod_fastrcnn_box_loss_bwd(const float* pred, const int* gt_classes, const fl
 #define SOD_BOX_LOSS_GIOU 0
 #define SOD_BOX_LOSS_ROTATED_IOU 1
 #define SOD_BOX_LOSS_ROTATED_GIOU 2
+#define SOD_BOX_LOSS_ROTATED_KLD 3
 int sod_rows_box_loss_fwd(const float* pred, int ld, const void* labels, int row_form, int K, const float* src, const float* gt, int R,
                           int kind, const float* weights, float scale_clamp, float* sum_out, float* ws, void* stream);
 int sod_rows_box_loss_bwd(const float* pred, int ld, const void* labels, int row_form, int K, const float* src, const float* gt, int R,
@@ -1002,6 +1004,27 @@ int sod_retina_rgiou_loss_bwd(const float* pred, int pitch, const int* gt_labels
 int sod_retina_rgiou_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
                                   int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
                                   const float* grad_num, const float* grad_den, float* dpred, void* stream);
+
+/* Gaussian KL-divergence box loss (csrc/gauss_box_loss.h, csrc/rotated_kld_loss.hip; layers.rotated_kld_loss, BBOX_REG_LOSS_TYPE
+ * "rotated_kld"; Yang et al., NeurIPS 2021).  A box (cx, cy, w, h, angle_deg) is the Gaussian with mean (cx, cy) and covariance
+ * R diag(w^2 / 4, h^2 / 4) R^T; D = KL(N_pred || N_target) and loss = 1 - 1 / (1 + ln(1 + D)) in [0, 1), 0 exactly when the Gaussians
+ * coincide.  Smooth wherever the sides are positive (no kinks, nothing clipped, no LDS); boxes that do not overlap keep a gradient; the
+ * value does not depend on how a box is written ((w, h, t), (h, w, t + 90) and t + 180 are one Gaussian); the angle's gradient grows with
+ * the squared aspect ratio.  Limits: a side of either box that is not positive or not finite gives NaN (value and gradient); a SQUARE box
+ * is an isotropic Gaussian, so its angle has no effect on the loss and gets gradient 0; quotients of two sides above 1.8e19 overflow.
+ * sod_rotated_kld_loss: the contract of sod_rotated_iou_loss (the angle's gradient per degree; P == 0: sum_out = 0, nothing else written).
+ * sod_retina_rkld_loss_{fwd,bwd,bwd_f32}: that of sod_retina_riou_loss_*, a clamped dw / dh having gradient exactly 0. */
+int sod_rotated_kld_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
+                         const float* grad_scale, float* dboxes1, float* ws, void* stream);
+int sod_retina_rkld_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                             int N, int R, int A, int num_classes, const float* weights5, float scale_clamp, float* sums2,
+                             float* normalizer, float momentum, float* ws, void* stream);
+int sod_retina_rkld_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                             int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                             const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream);
+int sod_retina_rkld_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                 int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                 const float* grad_num, const float* grad_den, float* dpred, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------
  * Minimum-area rectangles of polygon annotations (csrc/polygon_geom.hip; host side slenderobjdet_amd/structures/polygons.py): the

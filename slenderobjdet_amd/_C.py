@@ -204,6 +204,10 @@ _SIGS = {
     "sod_retina_rgiou_loss_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
     "sod_retina_rgiou_loss_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P],
     "sod_retina_rgiou_loss_bwd_f32": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P],
+    "sod_rotated_kld_loss": [_P, _P, _L, _P, _P, _P, _P, _P, _P],
+    "sod_retina_rkld_loss_fwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _F, _P, _P],
+    "sod_retina_rkld_loss_bwd": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P],
+    "sod_retina_rkld_loss_bwd_f32": [_P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _F, _P, _P, _P, _P],
 }
 _RESTYPES = {"sod_reduce_workspace_bytes": c_longlong, "sod_conv2d_wgrad_workspace_bytes": c_longlong, "sod_nms_workspace_bytes": c_longlong, "sod_batched_nms_workspace_bytes": c_longlong, "sod_version": c_char_p,
              "sod_coco_match_scratch_doubles": c_longlong, "sod_proposal_ar_scratch_floats": c_longlong,

@@ -2,7 +2,7 @@
 // from and compared with its matched gt box.  Two skeletons call them - retina_box_loss_kernel (retina_box_loss.hip: anchors of a pitched
 // per-pixel delta buffer) and rows_box_loss_kernel (rows_box_loss.hip: rows of sampled ROIs / sampled anchors) -, so there is one
 // definition of every loss and the two give the same bits for the same numbers.  The including file places this header inside its own
-// anonymous namespace, after common.h, rotated_iou.h, box_transform.h and box_pair_loss.h.
+// anonymous namespace, after common.h, rotated_iou.h, box_transform.h, box_pair_loss.h and gauss_box_loss.h.
 #pragma once
 
 struct BoxLossArgs {
@@ -42,6 +42,16 @@ struct GiouLoss {
   }
 };
 
+// The chain from the gradient gb w.r.t. the box that rot_apply_deltas decoded from source box s to the gradient g w.r.t. its five deltas
+// (gb[4] per degree): d cx / d dx = sw / wx, d w / d dw = w / ww and 0 where the clamp is active, d angle_deg / d da = 180 / (pi * wa).
+__device__ __forceinline__ void rot_delta_grad(const float* gb, const float* s, const float* box, const RotDecoded& k, const float* w, float* g) {
+  g[0] = gb[0] * s[2] / w[0];
+  g[1] = gb[1] * s[3] / w[1];
+  g[2] = k.cw ? 0.f : gb[2] * box[2] / w[2];
+  g[3] = k.ch ? 0.f : gb[3] * box[3] / w[3];
+  g[4] = gb[4] * 180.f / (SOD_PI * w[4]);
+}
+
 // The IoU is iou_rotated_lds (the number NMS, the matcher and the evaluator see); a positive whose IoU is 0 has no gradient.
 // HULL: with the hull term of rgiou_pair, which leaves such a positive a gradient.
 template <bool HULL>
@@ -61,13 +71,26 @@ struct RotIouLoss {
     else acc += 1.f - iou;
     if (BWD && (HULL || iou > 0.f)) {
       if constexpr (!HULL) riou_grad(box, t, iou, gb);
-      g[0] = gb[0] * s[2] / a.w.w[0];
-      g[1] = gb[1] * s[3] / a.w.w[1];
-      g[2] = k.cw ? 0.f : gb[2] * box[2] / a.w.w[2];
-      g[3] = k.ch ? 0.f : gb[3] * box[3] / a.w.w[3];
-      g[4] = gb[4] * 180.f / (SOD_PI * a.w.w[4]);
+      rot_delta_grad(gb, s, box, k, a.w.w, g);
     }
   }
 };
 using RiouLoss = RotIouLoss<false>;
 using RgiouLoss = RotIouLoss<true>;
+
+// The same decode, then the Gaussian KL-divergence loss of gauss_box_loss.h against the matched gt box: no clipping, so no LDS of its own.
+struct RkldLoss {
+  static constexpr int D = 5;
+  static constexpr bool ROT_LDS = false;
+  using Args = DecodeLossArgs;
+  template <bool BWD>
+  static __device__ __forceinline__ void positive(const Args& a, const float* p, long long r, long long i, P2* pts, float& acc, float* g) {
+    float d[5], s[5], t[5], box[5];
+#pragma unroll
+    for (int e = 0; e < 5; ++e) { d[e] = p[e]; s[e] = a.anchors[r * 5 + e]; t[e] = a.target[i * 5 + e]; }
+    const RotDecoded k = rot_apply_deltas(d, s, a.w.w, a.clampv, box);
+    float gb[5];
+    acc += rkld_pair<BWD>(box, t, gb);
+    if (BWD) rot_delta_grad(gb, s, box, k, a.w.w, g);
+  }
+};

@@ -7,6 +7,7 @@
 //   GiouLoss         sod_retina_giou_loss_*   Box2BoxTransform.apply_deltas, fvcore giou_loss against the matched gt box          ("giou")
 //   RiouLoss         sod_retina_riou_loss_*   Box2BoxTransformRotated.apply_deltas, 1 - rotated IoU against the matched gt box    ("rotated_iou")
 //   RgiouLoss        sod_retina_rgiou_loss_*  the same decode, 1 - IoU + (hull - union) / hull against the matched gt box         ("rotated_giou")
+//   RkldLoss         sod_retina_rkld_loss_*   the same decode, 1 - 1 / (1 + ln(1 + KL(N_box || N_gt))) of the boxes' Gaussians    ("rotated_kld")
 // A policy has: D; Args (BoxLossArgs plus its own fields); ROT_LDS (whether the kernel owns the 48 KB of clipping points of rotated_iou.h);
 // and positive<BWD>(a, p, r, i, pts, acc, g): for the positive anchor i = n*R + r whose deltas start at p, add the loss to acc (in place:
 // smooth-L1 adds element by element, and the running sum's bits depend on that) and, if BWD, write the D delta gradients to g (zeros before).
@@ -21,7 +22,8 @@ namespace {
 #include "rotated_iou.h"
 #include "box_transform.h"
 #include "box_pair_loss.h"
-#include "box_loss_policy.h"      // BoxLossArgs, DecodeLossArgs; GiouLoss, RiouLoss, RgiouLoss (shared with rows_box_loss.hip)
+#include "gauss_box_loss.h"
+#include "box_loss_policy.h"      // BoxLossArgs, DecodeLossArgs; GiouLoss, RiouLoss, RgiouLoss, RkldLoss (shared with rows_box_loss.hip)
 
 struct SmoothL1Args : BoxLossArgs { float beta; };
 
@@ -236,4 +238,23 @@ extern "C" int sod_retina_rgiou_loss_bwd_f32(const float* pred, int pitch, const
                                              const float* grad_num, const float* grad_den, float* dpred, void* stream) {
   DECODE_FILL(5, weights5);
   return launch_bwd<RgiouLoss>(a, grad_num, grad_den, dpred, stream);
+}
+
+extern "C" int sod_retina_rkld_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                        int N, int R, int A, int num_classes, const float* weights5, float scale_clamp, float* sums2,
+                                        float* normalizer, float momentum, float* ws, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_fwd<RkldLoss>(a, sums2, normalizer, momentum, ws, stream);
+}
+extern "C" int sod_retina_rkld_loss_bwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                        int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                        const float* grad_num, const float* grad_den, void* dpred_bf16, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_bwd<RkldLoss>(a, grad_num, grad_den, (__bf16*)dpred_bf16, stream);
+}
+extern "C" int sod_retina_rkld_loss_bwd_f32(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
+                                            int N, int R, int A, int num_classes, const float* weights5, float scale_clamp,
+                                            const float* grad_num, const float* grad_den, float* dpred, void* stream) {
+  DECODE_FILL(5, weights5);
+  return launch_bwd<RkldLoss>(a, grad_num, grad_den, dpred, stream);
 }

@@ -1,11 +1,11 @@
 // The fused decode + box regression loss over ROWS, forward and backward, for the R-CNN heads' BBOX_REG_LOSS_TYPE "giou" (D = 4),
-// "rotated_iou" and "rotated_giou" (D = 5): row i regresses from src[i] (a sampled proposal or a sampled anchor) towards gt[i], and its
+// "rotated_iou", "rotated_giou" and "rotated_kld" (D = 5): row i regresses from src[i] (a sampled proposal or a sampled anchor) towards gt[i], and its
 // deltas are D columns of the ld-wide row i of pred.  Two row forms say which rows count and which columns hold the deltas:
 //   SOD_ROWS_FRCNN  int32 labels; foreground = 0 <= label < K; columns [label * D, label * D + D)   (FastRCNNOutputLayers, class-specific)
 //   SOD_ROWS_RPN    int8 labels in {-1, 0, 1}; foreground = label == 1; columns [0, D)               (RPN / RRPN, the gathered sampled rows)
 // At a foreground row the kernel calls the policies of box_loss_policy.h - the code the RetinaNet kernels of retina_box_loss.hip call -,
 // so the same numbers give the same bits in both.  The skeleton is that kernel's: 256 threads, a grid-stride loop, one row per thread, the
-// 48 KB of clipping points only in the rotated instantiations, the forward sum through the reduce workspace (no float atomics: a call is
+// 48 KB of clipping points only in the rotated IoU instantiations, the forward sum through the reduce workspace (no float atomics: a call is
 // bit-reproducible).  Backward writes EVERY element of dpred (R, ld): a block first leaves the <= 256 x D scaled delta gradients of its
 // rows in LDS, then its threads walk the rows' 256 * ld consecutive floats together (coalesced) and store the gradient where a column
 // belongs to the row's class and zero elsewhere - other classes, pad columns [K * D, ld), non-foreground rows.
@@ -19,6 +19,7 @@ namespace {
 #include "rotated_iou.h"
 #include "box_transform.h"
 #include "box_pair_loss.h"
+#include "gauss_box_loss.h"
 #include "box_loss_policy.h"
 
 // DecodeLossArgs as the policies read it - pred, target = gt (R, D), anchors = src (R, D), w, clampv - with R rows of pitch ld and
@@ -104,7 +105,8 @@ int launch(const RowsArgs& a, float* sum_out, float* ws, const float* grad_scale
 int rows_box_loss(const float* pred, int ld, const void* labels, int row_form, int K, const float* src, const float* gt, int R, int kind,
                   const float* weights, float scale_clamp, float* sum_out, float* ws, const float* grad_scale, float scale_mul, float* dpred,
                   void* stream) {
-  if (kind != SOD_BOX_LOSS_GIOU && kind != SOD_BOX_LOSS_ROTATED_IOU && kind != SOD_BOX_LOSS_ROTATED_GIOU) return SOD_EARG;
+  if (kind != SOD_BOX_LOSS_GIOU && kind != SOD_BOX_LOSS_ROTATED_IOU && kind != SOD_BOX_LOSS_ROTATED_GIOU && kind != SOD_BOX_LOSS_ROTATED_KLD)
+    return SOD_EARG;
   if (row_form != SOD_ROWS_FRCNN && row_form != SOD_ROWS_RPN) return SOD_EARG;
   const int D = kind == SOD_BOX_LOSS_GIOU ? 4 : 5;
   if (row_form == SOD_ROWS_RPN) K = 1;
@@ -124,8 +126,11 @@ int rows_box_loss(const float* pred, int ld, const void* labels, int row_form, i
   if (kind == SOD_BOX_LOSS_ROTATED_IOU)
     return rpn ? launch<RiouLoss, true>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream)
                : launch<RiouLoss, false>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream);
-  return rpn ? launch<RgiouLoss, true>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream)
-             : launch<RgiouLoss, false>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream);
+  if (kind == SOD_BOX_LOSS_ROTATED_GIOU)
+    return rpn ? launch<RgiouLoss, true>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream)
+               : launch<RgiouLoss, false>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream);
+  return rpn ? launch<RkldLoss, true>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream)
+             : launch<RkldLoss, false>(a, sum_out, ws, grad_scale, scale_mul, dpred, stream);
 }
 
 }  // namespace

@@ -4,7 +4,7 @@
 def __getattr__(name):
     # ``from slenderobjdet_amd.layers import rotated_iou_loss`` without importing the loss module together with the package: what a
     # program loads when it imports a sub-module of ``layers`` stays what it was
-    if name in ("rotated_iou_loss", "rotated_giou_loss"):
+    if name in ("rotated_iou_loss", "rotated_giou_loss", "rotated_kld_loss"):
         from . import losses
 
         return getattr(losses, name)

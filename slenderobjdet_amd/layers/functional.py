@@ -1373,9 +1373,10 @@ def retina_targets(anchors, gt_boxes, gt_classes, matches, match_labels, num_cla
          ptr(gt_deltas_out), stream_ptr())
 
 
-# The fused box regression loss on the pitched delta buffer (csrc/retina_box_loss.hip), five kinds: smooth-L1 over D = 4 ("box") or 5
-# ("box5") deltas against the matched deltas; GIoU (D = 4, "giou"), rotated IoU (D = 5, "riou") and rotated GIoU (D = 5, "rgiou") of the
-# decoded box against the matched gt box.  A kind's extra arguments follow the target: (beta,) or (anchors, weights, scale_clamp).
+# The fused box regression loss on the pitched delta buffer (csrc/retina_box_loss.hip), six kinds: smooth-L1 over D = 4 ("box") or 5
+# ("box5") deltas against the matched deltas; GIoU (D = 4, "giou"), rotated IoU (D = 5, "riou"), rotated GIoU (D = 5, "rgiou") and the
+# Gaussian KL-divergence loss (D = 5, "rkld") of the decoded box against the matched gt box.  A kind's extra arguments follow the target:
+# (beta,) or (anchors, weights, scale_clamp).
 def _retina_loss_args(stem, D, extra, pred, pitch, gt_labels, target, N, R, A, num_classes, dpred=None):
     """Checks the buffers against N, R, A and pitch - the kernels index by those integers alone - and returns the C arguments up to the
     kind's extras.  The keep-alive of the weights' ctypes array is the returned list itself."""
@@ -1446,6 +1447,14 @@ def retina_rgiou_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, 
     _retina_loss_bwd("rgiou", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
 
 
+def retina_rkld_loss_fwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, normalizer, momentum):
+    return _retina_loss_fwd("rkld", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, normalizer, momentum)
+
+
+def retina_rkld_loss_bwd(pred, pitch, gt_labels, anchors, matched_boxes, N, R, A, num_classes, weights, scale_clamp, grad_num, grad_den, dpred):
+    _retina_loss_bwd("rkld", 5, (anchors, weights, scale_clamp), pred, pitch, gt_labels, matched_boxes, N, R, A, num_classes, grad_num, grad_den, dpred)
+
+
 # ----------------------------------------------------------------------------------------------- RotatedRetinaNet
 def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, labels, allow_low_quality, num_classes, weights, ws=None,
                          want_boxes=False):
@@ -1514,6 +1523,17 @@ def rotated_giou_loss_fwd(pred, target, want_elem=True):
 def rotated_giou_loss_bwd(pred, target, grad_scale=None):
     """grad_scale[0] * d sum(loss) / d pred (P, 5), the angle's column per degree; rows without overlap keep the hull term's gradient."""
     return _rotated_pair_loss_bwd("giou", pred, target, grad_scale)
+
+
+def rotated_kld_loss_fwd(pred, target, want_elem=True):
+    """1 - 1 / (1 + ln(1 + KL(N_pred || N_target))) of the pairs (pred[i], target[i]) of (P, 5) boxes, each box the Gaussian with mean
+    (cx, cy) and covariance R diag(w^2 / 4, h^2 / 4) R^T -> (elem (P) or None, sum (1)).  A side that is not positive or not finite: NaN."""
+    return _rotated_pair_loss_fwd("kld", pred, target, want_elem)
+
+
+def rotated_kld_loss_bwd(pred, target, grad_scale=None):
+    """grad_scale[0] * d sum(loss) / d pred (P, 5), the angle's column per degree (exactly 0 for a square prediction or target)."""
+    return _rotated_pair_loss_bwd("kld", pred, target, grad_scale)
 
 
 def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):
@@ -1894,18 +1914,22 @@ def fastrcnn_box_loss_bwd(pred, gt_classes, gt_deltas, K, beta, grad_scale, scal
     return d
 
 
-# The R-CNN heads' IoU box losses over rows (csrc/rows_box_loss.hip).  loss_type: the config's BBOX_REG_LOSS_TYPE; rows: "frcnn" (int32
+# The R-CNN heads' decoded-box losses over rows (csrc/rows_box_loss.hip).  loss_type: the config's BBOX_REG_LOSS_TYPE; rows: "frcnn" (int32
 # class labels, class-specific delta columns, K classes) or "rpn" (int8 labels in {-1, 0, 1}, D columns).
 ROWS_BOX_LOSS_KINDS = {"giou": (0, 4), "rotated_iou": (1, 5), "rotated_giou": (2, 5)}
+# ... and the Gaussian loss of csrc/gauss_box_loss.h, which is no IoU loss: a table of its own (tests/test_rcnn_box_loss_host.py holds the
+# table above to exactly the three IoU kinds); the wrappers below look a loss_type up in both.
+ROWS_GAUSS_LOSS_KINDS = {"rotated_kld": (3, 5)}
+_ROWS_KINDS = {**ROWS_BOX_LOSS_KINDS, **ROWS_GAUSS_LOSS_KINDS}
 _ROWS_FORMS = {"frcnn": (0, torch.int32), "rpn": (1, torch.int8)}
 
 
 def _rows_box_loss_args(loss_type, rows, pred, labels, K, src, gt, weights, scale_clamp):
     """Checks the buffers against each other - the kernel indexes by R, ld, K and D alone - and returns the C arguments up to scale_clamp.
     The keep-alive of the weights' ctypes array is the returned list itself."""
-    if loss_type not in ROWS_BOX_LOSS_KINDS or rows not in _ROWS_FORMS:
-        raise _C.SlenderHipError(f"rows_box_loss: loss_type {loss_type!r} must be one of {sorted(ROWS_BOX_LOSS_KINDS)}, rows {rows!r} 'frcnn' or 'rpn'")
-    (kind, D), (form, ldt) = ROWS_BOX_LOSS_KINDS[loss_type], _ROWS_FORMS[rows]
+    if loss_type not in _ROWS_KINDS or rows not in _ROWS_FORMS:
+        raise _C.SlenderHipError(f"rows_box_loss: loss_type {loss_type!r} must be one of {sorted(_ROWS_KINDS)}, rows {rows!r} 'frcnn' or 'rpn'")
+    (kind, D), (form, ldt) = _ROWS_KINDS[loss_type], _ROWS_FORMS[rows]
     _chk(pred, torch.float32, "pred"); _chk(labels, ldt, "labels"); _chk(src, torch.float32, "src"); _chk(gt, torch.float32, "gt")
     K = int(K) if rows == "frcnn" else 1
     if not (pred.dim() == 2 and labels.numel() == pred.shape[0] and tuple(src.shape) == (pred.shape[0], D) and src.shape == gt.shape

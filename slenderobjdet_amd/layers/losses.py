@@ -4,6 +4,7 @@
   iou_loss                  — slender_det/layers/iou_loss.py:4-37
   rotated_iou_loss          — 1 - IoU of rotated box pairs (no counterpart in the reference), csrc/rotated_iou_loss.hip
   rotated_giou_loss         — the same with the convex-hull term of GIoU, which keeps a gradient for pairs that do not overlap
+  rotated_kld_loss          — the Kullback-Leibler divergence of the boxes' Gaussians (Yang et al., NeurIPS 2021), csrc/gauss_box_loss.h
 """
 import torch
 from torch.autograd.function import once_differentiable
@@ -102,7 +103,7 @@ def bce_with_logits_fg_sum(logits, targets, labels, bg_label):
 
 
 class _RotatedIouLossFn(torch.autograd.Function):
-    """``ops``: the (fwd, bwd) pair of the op layer - rotated IoU or rotated GIoU."""
+    """``ops``: the (fwd, bwd) pair of the op layer - rotated IoU, rotated GIoU or the Gaussian KL divergence."""
 
     @staticmethod
     def forward(ctx, pred, target, reduction, ops):
@@ -150,3 +151,19 @@ def rotated_giou_loss(pred, target, reduction="sum"):
     IoU the loss has kinks where a corner enters or leaves the hull (collinear or coincident corners: identical boxes, equal angles
     with a shared edge line); the value is right there and the gradient is the one of a side (csrc/box_pair_loss.h says which)."""
     return _rotated_pair_loss("rotated_giou_loss", (HF.rotated_giou_loss_fwd, HF.rotated_giou_loss_bwd), pred, target, reduction)
+
+
+def rotated_kld_loss(pred, target, reduction="sum"):
+    """The Gaussian KL-divergence loss of (P, 5) rotated boxes (cx, cy, w, h, angle_deg) (Yang et al., NeurIPS 2021).  A box is the
+    Gaussian N(mu, S) with mu = (cx, cy) and S = R diag(w^2 / 4, h^2 / 4) R^T, R turning the width axis to (cos t, -sin t); then
+
+        D = KL(N_pred || N_target) = 1/2 (mu_p - mu_t)^T S_t^-1 (mu_p - mu_t) + 1/2 Tr(S_t^-1 S_p) + 1/2 ln(|S_t| / |S_p|) - 1
+        loss = 1 - 1 / (1 + ln(1 + D))            in [0, 1), 0 exactly when the two Gaussians coincide.
+
+    The gradient flows to ``pred`` only, its angle column per degree.  The loss is smooth wherever the sides are positive (no kinks:
+    nothing is clipped), keeps a gradient for boxes that do not overlap, and its angle gradient grows with the squared aspect ratio.
+    Invariances: it depends on the Gaussian, not on how the box is written - (w, h, t), (h, w, t + 90) and t +- 180 give the same value.
+    Limits: a SQUARE box is an isotropic Gaussian, so its angle has no effect on the loss and gets gradient 0 (if either box is square
+    the angle column is exactly 0) - the loss cannot orient a square; a side of either box that is not positive or not finite gives NaN,
+    value and gradient."""
+    return _rotated_pair_loss("rotated_kld_loss", (HF.rotated_kld_loss_fwd, HF.rotated_kld_loss_bwd), pred, target, reduction)

@@ -6,9 +6,9 @@ from ..layers import functional as HF
 
 _DEFAULT_SCALE_CLAMP = math.log(1000.0 / 16)
 
-# MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE and MODEL.RPN.BBOX_REG_LOSS_TYPE by box_dim: smooth-L1 on the deltas, or an IoU loss of the decoded
-# box (csrc/rows_box_loss.hip).  detectron2's "diou" / "ciou" are not built.
-BOX_REG_LOSS_TYPES = {4: ("smooth_l1", "giou"), 5: ("smooth_l1", "rotated_iou", "rotated_giou")}
+# MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE and MODEL.RPN.BBOX_REG_LOSS_TYPE by box_dim: smooth-L1 on the deltas, or an IoU loss / the Gaussian
+# KL-divergence loss ("rotated_kld") of the decoded box (csrc/rows_box_loss.hip).  detectron2's "diou" / "ciou" are not built.
+BOX_REG_LOSS_TYPES = {4: ("smooth_l1", "giou"), 5: ("smooth_l1", "rotated_iou", "rotated_giou", "rotated_kld")}
 
 
 class Box2BoxTransform:

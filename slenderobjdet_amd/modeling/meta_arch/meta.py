@@ -602,7 +602,8 @@ class AnchorHead(nn.Module):
         self.max_detections_per_image = cfg.TEST.DETECTIONS_PER_IMAGE
         self.box_reg_loss_type = h.BBOX_REG_LOSS_TYPE
         if self.box_reg_loss_type not in ("smooth_l1", "giou"):
-            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}'")
+            raise ValueError(f"Invalid bbox reg loss type '{self.box_reg_loss_type}': AnchorHead's MODEL.META_ARCH.BBOX_REG_LOSS_TYPE must be "
+                             f"'smooth_l1' or 'giou'")
         if self.feat_adaption not in (None, "none", "unsupervised", "split", "supervised"):
             raise AssertionError(self.feat_adaption)                    # anchor_head.py:104
         if self.res_refine:

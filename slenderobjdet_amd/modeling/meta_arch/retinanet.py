@@ -92,11 +92,12 @@ class RetinaNetHead(nn.Module):
 
 def _box_loss_kind(model, hw):
     """The model's box regression loss as the leading arguments of HF._retina_loss_fwd / _bwd: (symbol stem, deltas per anchor, the
-    kind's extra arguments).  For the IoU kinds the targets (``gt_deltas``) hold the matched gt BOXES (N, R, D)."""
+    kind's extra arguments).  For the decoded-box kinds (IoU, KL divergence) the targets (``gt_deltas``) hold the matched gt BOXES (N, R, D)."""
     if model.box_reg_loss_type == "giou":
         return "giou", 4, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
-    if model.box_reg_loss_type in ("rotated_iou", "rotated_giou"):        # RotatedRetinaNet
-        return ("riou" if model.box_reg_loss_type == "rotated_iou" else "rgiou"), 5, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
+    if model.box_reg_loss_type in ("rotated_iou", "rotated_giou", "rotated_kld"):        # RotatedRetinaNet
+        stem = {"rotated_iou": "riou", "rotated_giou": "rgiou", "rotated_kld": "rkld"}[model.box_reg_loss_type]
+        return stem, 5, (model.anchors_for(hw), model.bbox_reg_weights, model.scale_clamp)
     D = getattr(model.head, "box_dim", 4)
     return ("box5" if D == 5 else "box"), D, (model.smooth_l1_loss_beta,)
 
@@ -191,8 +192,9 @@ class RetinaNetBase(nn.Module):
         self.focal_loss_alpha, self.focal_loss_gamma = r.FOCAL_LOSS_ALPHA, r.FOCAL_LOSS_GAMMA
         self.smooth_l1_loss_beta = r.SMOOTH_L1_LOSS_BETA
         self.box_reg_loss_type = r.BBOX_REG_LOSS_TYPE
-        if self.box_reg_loss_type not in self.box_reg_loss_types:
-            raise ValueError(f"{type(self).__name__}: MODEL.RETINANET.BBOX_REG_LOSS_TYPE must be one of {self.box_reg_loss_types}, "
+        if self.box_reg_loss_type not in self.box_reg_loss_types + self.gauss_box_reg_loss_types:
+            raise ValueError(f"{type(self).__name__}: MODEL.RETINANET.BBOX_REG_LOSS_TYPE must be one of "
+                             f"{self.box_reg_loss_types + self.gauss_box_reg_loss_types}, "
                              f"got {self.box_reg_loss_type!r}")                                 # retina_rotated.py:243-244
         self.scale_clamp = math.log(1000.0 / 16)
         self.iou_thresholds, self.iou_labels = list(r.IOU_THRESHOLDS), list(r.IOU_LABELS)
@@ -215,6 +217,7 @@ class RetinaNetBase(nn.Module):
 
     box_dim = 4
     box_reg_loss_types = ("smooth_l1", "giou")
+    gauss_box_reg_loss_types = ()          # the Gaussian losses of rotated boxes a sub-class adds to the set above
 
     @staticmethod
     def num_cell_anchors(cfg):

@@ -12,7 +12,9 @@ pairwise_iou (:276) and its head is 4 columns wide (:437).  There is no upstream
             "rotated_iou" the sum of 1 - IoU(decoded box, matched gt) over the positives (the IoU the detector is scored by; no gradient
             for a positive whose decoded box does not overlap its gt), or with "rotated_giou" that sum plus (C - U) / C, C the area of
             the convex hull of the two boxes and U their union (such a positive then has the hull term's gradient, which pulls the box
-            towards its gt); all / the EMA loss_normalizer
+            towards its gt), or with "rotated_kld" the sum of 1 - 1 / (1 + ln(1 + KL)) over the positives, KL the Kullback-Leibler
+            divergence of the decoded box's Gaussian from its gt's (csrc/gauss_box_loss.h: smooth, a gradient without overlap, an angle
+            gradient that grows with the squared aspect ratio; a square box's angle gets none); all / the EMA loss_normalizer
   inference per level sigmoid + threshold + top-k (dense_topk_select), Box2BoxTransformRotated.apply_deltas on the survivors, class-aware
             rotated NMS, top DETECTIONS_PER_IMAGE; Instances carry RotatedBoxes
 
@@ -34,6 +36,7 @@ from .retinanet import RetinaNetBase
 class RotatedRetinaNet(RetinaNetBase):
     box_dim = 5
     box_reg_loss_types = ("smooth_l1", "rotated_iou", "rotated_giou")
+    gauss_box_reg_loss_types = ("rotated_kld",)
 
     def __init__(self, cfg):
         r, ag = cfg.MODEL.RETINANET, cfg.MODEL.ANCHOR_GENERATOR
@@ -41,8 +44,8 @@ class RotatedRetinaNet(RetinaNetBase):
             raise ValueError(f"RotatedRetinaNet: MODEL.ANCHOR_GENERATOR.NAME must be 'RotatedAnchorGenerator', got {ag.NAME!r}")
         if len(r.BBOX_REG_WEIGHTS) != 5:
             raise ValueError(f"RotatedRetinaNet: MODEL.RETINANET.BBOX_REG_WEIGHTS must hold five weights (dx, dy, dw, dh, da), got {tuple(r.BBOX_REG_WEIGHTS)}")
-        if r.BBOX_REG_LOSS_TYPE not in self.box_reg_loss_types:
-            raise ValueError(f"RotatedRetinaNet: MODEL.RETINANET.BBOX_REG_LOSS_TYPE must be 'smooth_l1', 'rotated_iou' or 'rotated_giou', "
+        if r.BBOX_REG_LOSS_TYPE not in self.box_reg_loss_types + self.gauss_box_reg_loss_types:
+            raise ValueError(f"RotatedRetinaNet: MODEL.RETINANET.BBOX_REG_LOSS_TYPE must be 'smooth_l1', 'rotated_iou', 'rotated_giou' or 'rotated_kld', "
                              f"got {r.BBOX_REG_LOSS_TYPE!r}")
         A = self.num_cell_anchors(cfg)
         if A * r.NUM_CLASSES % 8:
@@ -68,7 +71,7 @@ class RotatedRetinaNet(RetinaNetBase):
     @torch.no_grad()
     def label_anchors(self, anchors, gt_instances):
         """-> gt_labels (N, R) int32 in {-1, 0..K-1, K} and gt_deltas (N, R, 5): two launches for the whole batch.  The gts are padded to
-        the largest image's count from their shapes (known to the host); nothing is read back from the device.  For "rotated_iou" and "rotated_giou" the
+        the largest image's count from their shapes (known to the host); nothing is read back from the device.  For "rotated_iou", "rotated_giou" and "rotated_kld" the
         second output holds the matched gt boxes themselves (the loss compares decoded boxes with them); the labels do not change."""
         N = len(gt_instances)
         lens = [len(g) for g in gt_instances]
@@ -82,7 +85,7 @@ class RotatedRetinaNet(RetinaNetBase):
             classes.view(-1).index_copy_(0, slot, torch.cat([g.gt_classes.to(torch.int32).view(-1) for g in gt_instances]))
         counts = torch.tensor(lens, dtype=torch.int32).to(dev, non_blocking=True)
         return HF.retina_label_rotated(anchors, boxes, classes, counts, self.iou_thresholds, self.iou_labels, True, self.num_classes,
-                                       self.bbox_reg_weights, want_boxes=self.box_reg_loss_type in ("rotated_iou", "rotated_giou"))
+                                       self.bbox_reg_weights, want_boxes=self.box_reg_loss_type in ("rotated_iou", "rotated_giou", "rotated_kld"))
 
     @torch.no_grad()
     def inference(self, level_hw, cls_buf, box_buf, offs, image_sizes):

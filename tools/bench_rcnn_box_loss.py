@@ -1,7 +1,7 @@
 """The R-CNN heads' box regression losses (MODEL.ROI_BOX_HEAD.BBOX_REG_LOSS_TYPE / MODEL.RPN.BBOX_REG_LOSS_TYPE) on the rotated R-CNN of
 configs/rotated/faster_R_101.yaml at the benchmark's settings (batch 16, 1333 x 800 images, R50-FPN, bf16 product path, synthetic rotated
 batches, bench.train_step with prefetch and the warm-up schedule), one card:
-  * us per call of the row kernels ``sod_rows_box_loss_{fwd,bwd}`` ("rotated_iou", "rotated_giou") beside the smooth-L1 kernels they stand
+  * us per call of the row kernels ``sod_rows_box_loss_{fwd,bwd}`` ("rotated_iou", "rotated_giou", "rotated_kld") beside the smooth-L1 kernels they stand
     in for, at the step's real row counts: Fast R-CNN rows 16 x 512 = 8 192 of K = 80 classes (ld = 400, a quarter foreground) beside
     ``sod_fastrcnn_box_loss_*``, RPN rows 16 x 256 = 4 096 (ld = 5, half positive) beside ``sod_rpn_loc_loss_*``; calls issued back to back
     from Python, device events, warm-up, three alternating windows of --calls calls each;
@@ -10,7 +10,7 @@ batches, bench.train_step with prefetch and the warm-up schedule), one card:
 alternating runs with this tree's; the kernel part is skipped where that checkout has no row kernels.  Prints the card's shader clock
 with the figures.
 
-    python tools/bench_rcnn_box_loss.py [--box-loss smooth_l1|rotated_iou|rotated_giou] [--steps 20] [--warmup 5] [--calls 50]
+    python tools/bench_rcnn_box_loss.py [--box-loss smooth_l1|rotated_iou|rotated_giou|rotated_kld] [--steps 20] [--warmup 5] [--calls 50]
                                         [--skip-kernels] [--skip-step] [--root DIR] [--out FILE]
 """
 import argparse
@@ -24,7 +24,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--calls", type=int, default=50, help="timed calls per window of the kernel comparison (three windows per entry point)")
-ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou"], default="smooth_l1", help="the loss of both stages in the timed step")
+ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou", "rotated_kld"], default="smooth_l1", help="the loss of both stages in the timed step")
 ap.add_argument("--skip-kernels", action="store_true", help="only the training step")
 ap.add_argument("--skip-step", action="store_true", help="only the kernel comparison")
 ap.add_argument("--root", default=None, help="checkout to import slenderobjdet_amd and bench from (default: this one)")
@@ -87,7 +87,8 @@ if not args.skip_kernels and hasattr(HF, "rows_box_loss_fwd"):
         "rpn_loc_loss_fwd (smooth_l1)": lambda: HF.rpn_loc_loss_fwd(pred2, dl2, lab8, 0.0),
         "rpn_loc_loss_bwd (smooth_l1)": lambda: HF.rpn_loc_loss_bwd(pred2, dl2, lab8, 0.0, one, 1.0 / R2),
     }
-    for kind in ("rotated_iou", "rotated_giou"):
+    built = {**HF.ROWS_BOX_LOSS_KINDS, **getattr(HF, "ROWS_GAUSS_LOSS_KINDS", {})}          # --root: a checkout without the newer kinds
+    for kind in (k for k in ("rotated_iou", "rotated_giou", "rotated_kld") if k in built):
         entries[f"rows_box_loss_fwd frcnn ({kind})"] = lambda kind=kind: HF.rows_box_loss_fwd(kind, "frcnn", pred1, cls, K, src1, gt1, W_ROI, CLAMP)
         entries[f"rows_box_loss_bwd frcnn ({kind})"] = lambda kind=kind: HF.rows_box_loss_bwd(kind, "frcnn", pred1, cls, K, src1, gt1, W_ROI, CLAMP, one, 1.0 / R1)
         entries[f"rows_box_loss_fwd rpn ({kind})"] = lambda kind=kind: HF.rows_box_loss_fwd(kind, "rpn", pred2, lab8, 1, src2, gt2, W_RPN, CLAMP)

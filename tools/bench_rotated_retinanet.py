@@ -5,10 +5,15 @@ synthetic batches, bench.train_step with prefetch and the reference's warm-up sc
     on the same inputs, the two alternating; the labels of the two are compared first;
   * img/s of a full training step of the three classes, built one after the other in this process.
 Device events, warm-up, >= 20 timed calls; prints the card's shader clock with the figures.
-``--box-loss rotated_iou`` / ``rotated_giou`` trains RotatedRetinaNet's box regression with the rotated IoU / GIoU loss
-(MODEL.RETINANET.BBOX_REG_LOSS_TYPE) instead of smooth-L1; ``--rotated-only`` times RotatedRetinaNet's step alone (alternating runs of the two box losses, one process each).
+``--box-loss rotated_iou`` / ``rotated_giou`` / ``rotated_kld`` trains RotatedRetinaNet's box regression with the rotated IoU / GIoU /
+Gaussian KL-divergence loss (MODEL.RETINANET.BBOX_REG_LOSS_TYPE) instead of smooth-L1; ``--rotated-only`` times RotatedRetinaNet's step
+alone (alternating runs of the box losses, one process each).  ``--box-kernels`` adds us per call of the box-loss kernels of the three
+decoded-box losses, the entry points alternating: the pair operators ``sod_rotated_{iou,giou,kld}_loss`` (forward, forward + backward;
+P = the step's 886 positives, 65 536 and 1 048 576 pairs) and the fused ``sod_retina_{riou,rgiou,rkld}_loss_{fwd,bwd}`` on the step's own
+geometry (N * R = 16 * 403 200 anchors, the labeller's labels and matched boxes).
 
-    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--box-loss smooth_l1|rotated_iou|rotated_giou] [--rotated-only] [--out FILE]
+    python tools/bench_rotated_retinanet.py [--steps 20] [--warmup 5] [--skip-step] [--box-loss smooth_l1|rotated_iou|rotated_giou|rotated_kld]
+                                            [--rotated-only] [--box-kernels] [--out FILE]
 """
 import argparse
 import json
@@ -30,7 +35,8 @@ ap.add_argument("--steps", type=int, default=20)
 ap.add_argument("--warmup", type=int, default=5)
 ap.add_argument("--calls", type=int, default=20, help="timed calls per round of the labelling comparison (three rounds)")
 ap.add_argument("--skip-step", action="store_true", help="only the labelling comparison")
-ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou"], default="smooth_l1", help="RotatedRetinaNet's box regression loss")
+ap.add_argument("--box-loss", choices=["smooth_l1", "rotated_iou", "rotated_giou", "rotated_kld"], default="smooth_l1", help="RotatedRetinaNet's box regression loss")
+ap.add_argument("--box-kernels", action="store_true", help="also time the pair operators and the fused kernels of the decoded-box losses")
 ap.add_argument("--rotated-only", action="store_true", help="time RotatedRetinaNet's training step only, not the two other classes")
 ap.add_argument("--out", default=None, help="also write the JSON result to this file")
 args = ap.parse_args()
@@ -126,6 +132,51 @@ out["labelling"] = {"N": N, "R": R, "gts": int(sum(counts)), "Gmax": Gmax, "labe
                     "launches": {"fused": 2, "composition_kernels": 3 * N}}
 print(f"labelling N = {N}, R = {R}, {sum(counts)} gts (max {Gmax}): fused {sum(tf) / 3:8.1f} us {[round(t, 1) for t in tf]} | per-image composition "
       f"{sum(tc) / 3:8.1f} us {[round(t, 1) for t in tc]} | labels equal: {same}, {int(pos.sum())} positives, max delta difference {dmax:.3g}", flush=True)
+
+# ---------------------------------------------------------------------------------------------- box-loss kernels
+if args.box_kernels:
+    g = torch.Generator().manual_seed(2)
+    kt = {}
+
+    def alternate(entries, calls):
+        for fn in entries.values():
+            for _ in range(3):
+                fn()
+        torch.cuda.synchronize()
+        t = {k: [] for k in entries}
+        for _ in range(3):
+            for k, fn in entries.items():
+                t[k].append(window(fn, calls))
+        for k, v in t.items():
+            kt[k] = [round(x, 1) for x in v]
+            print(f"  {k:44s} {sum(v) / len(v):9.1f} us  {[round(x, 1) for x in v]}", flush=True)
+
+    for P in (886, 65536, 1048576):
+        gt = torch.cat([16 + 1200 * torch.rand(P, 2, generator=g), 8 + 200 * torch.rand(P, 1, generator=g), 4 + 40 * torch.rand(P, 1, generator=g),
+                        360 * torch.rand(P, 1, generator=g) - 180], 1)
+        pr = gt + torch.cat([4 * torch.randn(P, 2, generator=g), 6 * torch.randn(P, 2, generator=g).abs(), 8 * torch.randn(P, 1, generator=g)], 1)
+        pr, gt = pr.to(dev), gt.to(dev)
+        entries = {}
+        for stem in ("iou", "giou", "kld"):
+            fwd, bwd = getattr(HF, f"rotated_{stem}_loss_fwd"), getattr(HF, f"rotated_{stem}_loss_bwd")
+            entries[f"rotated_{stem}_loss fwd P={P}"] = lambda fwd=fwd: fwd(pr, gt)
+            entries[f"rotated_{stem}_loss fwd+bwd P={P}"] = lambda fwd=fwd, bwd=bwd: (fwd(pr, gt), bwd(pr, gt))
+        print(f"pair operators, P = {P}, three windows of {args.calls} calls:", flush=True)
+        alternate(entries, args.calls)
+    lab_b, mb = HF.retina_label_rotated(anchors, pb, pc, cnt, THR, LAB, True, K, W5, ws=ws, want_boxes=True)
+    A = R // sum(h * w for h, w in level_hw)
+    pitch = (A * 5 + 7) // 8 * 8
+    pred = (0.1 * torch.randn(N, R // A, pitch, generator=g)).to(dev)
+    dpred = torch.empty(N, R // A, pitch, dtype=HF.ACT_DTYPE, device=dev)
+    nrm, one = torch.full((1,), 100.0, device=dev), torch.ones(1, device=dev)
+    entries = {}
+    for stem in ("riou", "rgiou", "rkld"):
+        fwd, bwd = getattr(HF, f"retina_{stem}_loss_fwd"), getattr(HF, f"retina_{stem}_loss_bwd")
+        entries[f"retina_{stem}_loss_fwd"] = lambda fwd=fwd: fwd(pred, pitch, lab_b, anchors, mb, N, R, A, K, W5, 4.135166556742356, nrm, 1.0)
+        entries[f"retina_{stem}_loss_bwd"] = lambda bwd=bwd: bwd(pred, pitch, lab_b, anchors, mb, N, R, A, K, W5, 4.135166556742356, one, nrm, dpred)
+    print(f"fused kernels, N * R = {N} * {R}, A = {A}, pitch {pitch}, {int(((lab_b >= 0) & (lab_b != K)).sum())} positives:", flush=True)
+    alternate(entries, args.calls)
+    out["box_kernels_us"] = kt
 
 # ---------------------------------------------------------------------------------------------- training steps
 if not args.skip_step:
