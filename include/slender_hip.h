@@ -486,10 +486,13 @@ int sod_roi_align_fwd_f32(const float* x, const float* rois, float* out, int R, 
 int sod_roi_align_bwd(const float* dout, const float* rois, float* dx, int R, int N, int H, int W, int C, int PH, int PW,
                       float spatial_scale, int sampling_ratio, int rotated, void* stream);
 /* fvcore.nn.giou_loss(boxes1, boxes2, eps) on XYXY (retina_rotated.py:240): per-row loss, optional sum, optional gradient
- * w.r.t. boxes1 scaled by grad_scale[0]. */
+ * w.r.t. boxes1 scaled by grad_scale[0].  One of the five pair operators (csrc/pair_loss.h: one kernel skeleton, the GiouXyxyPair
+ * policy; the others are sod_smooth_l1_loss and sod_rotated_{iou,giou,kld}_loss), which share one argument rule: P == 0 is legal, with
+ * NULL inputs too - sum_out[0] = 0 if asked, nothing else written; P > 0 needs both inputs, sum_out needs ws. */
 int sod_giou_loss_xyxy(const float* boxes1, const float* boxes2, long long P, float eps, float* elem_out, float* sum_out,
                        const float* grad_scale, float* dboxes1, float* ws, void* stream);
-/* fvcore.nn.smooth_l1_loss(input, target, beta) (retina_rotated.py:229, rpd.py:389-395) */
+/* fvcore.nn.smooth_l1_loss(input, target, beta) (retina_rotated.py:229, rpd.py:389-395): the pair operator of width 1 (SmoothL1Pair),
+ * one element a pair; n == 0 as P == 0 above. */
 int sod_smooth_l1_loss(const float* input, const float* target, long long n, float beta, float* elem_out, float* sum_out,
                        const float* grad_scale, float* dinput, float* ws, void* stream);
 /* pairwise_iou + Matcher([lo,hi],[l0,l1,l2],allow_low_quality_matches) of RetinaNet.label_anchors (retina_rotated.py:251-295)
@@ -955,7 +958,8 @@ int sod_retina_decode_rotated(const float* pred, int pitch, const float* anchors
  * Rotated IoU box loss (csrc/rotated_iou_loss.hip; layers.rotated_iou_loss, RotatedRetinaNet's BBOX_REG_LOSS_TYPE "rotated_iou"):
  * loss = 1 - IoU(pred, target) on (cx, cy, w, h, angle_deg) boxes.  The IoU is the one of sod_box_iou_rotated, to the bit.
  *
- * sod_rotated_iou_loss: the pair operator, the rotated sibling of sod_giou_loss_xyxy.  elem_out[i] = 1 - IoU(boxes1[i], boxes2[i])
+ * sod_rotated_iou_loss: the pair operator, the rotated sibling of sod_giou_loss_xyxy (RotIouPair<false> of the same skeleton; the
+ *   same argument rule).  elem_out[i] = 1 - IoU(boxes1[i], boxes2[i])
  *   (optional), sum_out[0] = their sum (optional; needs ws), dboxes1 (P, 5) = grad_scale[0] * d loss / d boxes1 (optional; grad_scale
  *   NULL = 1); the angle's gradient is per degree.  A row whose forward IoU is exactly 0 (disjoint boxes, an area below 1e-14, the
  *   early-outs of the IoU) gets five zeros: the loss has NO gradient for boxes that do not overlap.  The gradient is the boundary
@@ -992,7 +996,7 @@ int sod_retina_label_rotated_boxes(const float* anchors, int R, const float* gt_
  * collinear candidates the farthest is the next vertex, of coincident ones the first (the target's before the prediction's), and the
  * gradient is that of the shoelace sum over the walked vertices - at such a tie a one-sided derivative.  Besides the kinks of the IoU
  * the loss has kinks where a corner enters or leaves the hull.
- * sod_rotated_giou_loss: the contract of sod_rotated_iou_loss.  sod_retina_rgiou_loss_{fwd,bwd,bwd_f32}: that of sod_retina_riou_loss_*. */
+ * sod_rotated_giou_loss: the contract of sod_rotated_iou_loss (RotIouPair<true>).  sod_retina_rgiou_loss_{fwd,bwd,bwd_f32}: that of sod_retina_riou_loss_*. */
 int sod_rotated_giou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
                           const float* grad_scale, float* dboxes1, float* ws, void* stream);
 int sod_retina_rgiou_loss_fwd(const float* pred, int pitch, const int* gt_labels, const float* anchors, const float* matched_boxes,
@@ -1012,7 +1016,8 @@ int sod_retina_rgiou_loss_bwd_f32(const float* pred, int pitch, const int* gt_la
  * value does not depend on how a box is written ((w, h, t), (h, w, t + 90) and t + 180 are one Gaussian); the angle's gradient grows with
  * the squared aspect ratio.  Limits: a side of either box that is not positive or not finite gives NaN (value and gradient); a SQUARE box
  * is an isotropic Gaussian, so its angle has no effect on the loss and gets gradient 0; quotients of two sides above 1.8e19 overflow.
- * sod_rotated_kld_loss: the contract of sod_rotated_iou_loss (the angle's gradient per degree; P == 0: sum_out = 0, nothing else written).
+ * sod_rotated_kld_loss: the contract of sod_rotated_iou_loss (RkldPair, an instantiation without the clipping's LDS; the angle's gradient
+ *   per degree).
  * sod_retina_rkld_loss_{fwd,bwd,bwd_f32}: that of sod_retina_riou_loss_*, a clamped dw / dh having gradient exactly 0. */
 int sod_rotated_kld_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
                          const float* grad_scale, float* dboxes1, float* ws, void* stream);

@@ -1,6 +1,6 @@
 // The IoU losses of ONE box pair (GIoU of XYXY boxes, rotated IoU, rotated GIoU) and their gradients w.r.t. the first box, as device code:
-// shared by the pair operators (giou_xyxy_kernel of detection_ops.hip, rotated_iou_loss_kernel of rotated_iou_loss.hip) and the fused RetinaNet box loss
-// (retina_box_loss.hip).  The including file places this header inside its own anonymous namespace (after common.h), like rotated_iou.h.
+// shared by the pair operators (the GiouXyxyPair policy of detection_ops.hip and RotIouPair of rotated_iou_loss.hip, under the skeleton of
+// pair_loss.h) and the fused box losses (box_loss_policy.h).  The including file places this header inside its own anonymous namespace (after common.h), like rotated_iou.h.
 #pragma once
 
 // fvcore giou_loss of one XYXY pair; g (may be null): its gradient w.r.t. a.  max/min ties split like torch.

@@ -2,7 +2,7 @@
 // (sources absent from the reference tree; semantics restated in SURVEY.md Appendix C.3, C.4, C.5, C.13, C.14):
 //   roi_align fwd/bwd        detectron2 ROIAlign(aligned=True) used by ROIPooler (roi_heads/roi_heads.py:48-53)
 //   roi_align_rotated fwd    detectron2 ROIAlignRotated (configs/rotated/Base-RRCNN-FPN.yaml:31-36)
-//   giou / smooth-L1         fvcore.nn.giou_loss / smooth_l1_loss (retina_rotated.py:229,240; rpd.py:389-395)
+//   giou / smooth-L1         fvcore.nn.giou_loss / smooth_l1_loss (retina_rotated.py:229,240; rpd.py:389-395): pair policies of pair_loss.h
 //   anchor labelling         pairwise_iou + Matcher(thresholds, labels, allow_low_quality_matches) (retina_rotated.py:251-295)
 // All are HBM/latency-bound gather kernels: coalesced 16-B channel vectors, wavefront reductions, no MFMA.
 #include "common.h"
@@ -14,6 +14,7 @@ namespace {
 #include "rotated_iou.h"
 #include "box_transform.h"      // xyxy_get_deltas
 #include "box_pair_loss.h"      // giou_pair
+#include "pair_loss.h"          // pair_loss_kernel, launch_pairs
 
 __global__ __launch_bounds__(256) void pairwise_iou_rotated_kernel(const float* __restrict__ b1, int n1, const float* __restrict__ b2, int n2,
                                                                    float* __restrict__ out) {
@@ -245,44 +246,31 @@ __global__ __launch_bounds__(256) void roi_align_bwd_tile_kernel(const RoiArgs a
 }
 
 // ---------------------------------------------------------------------------------------------- box losses on XYXY
-// fvcore giou_loss (eps 1e-7): per-row loss and gradient w.r.t. boxes1
-__global__ __launch_bounds__(256) void giou_xyxy_kernel(const float* __restrict__ b1, const float* __restrict__ b2, long long P, float eps,
-                                                        float* __restrict__ elem, float* __restrict__ part, const float* __restrict__ gscale,
-                                                        float* __restrict__ d1) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  const float gs = gscale ? gscale[0] : 1.f;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) {
-    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(b1 + i * 4), b = *reinterpret_cast<const f32x4_t*>(b2 + i * 4);
-    float g[4];
-    const float l = giou_pair(a, b, eps, d1 ? g : nullptr);
-    if (elem) elem[i] = l;
-    acc += l;
-    if (d1) *reinterpret_cast<f32x4_t*>(d1 + i * 4) = f32x4_t{g[0] * gs, g[1] * gs, g[2] * gs, g[3] * gs};
+// the pair policies of pair_loss.h.  fvcore giou_loss (eps 1e-7): per-row loss and gradient w.r.t. boxes1
+struct GiouXyxyPair {
+  static constexpr int W = 4;
+  using Lds = void;
+  static constexpr int LDS_PER_LANE = 0;
+  static __device__ __forceinline__ float pair(const float* a, const float* b, float eps, void*, bool want_grad, float* g) {
+    return giou_pair(a, b, eps, want_grad ? g : nullptr);
   }
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0 && part) part[blockIdx.x] = acc;
-}
+};
 
-__global__ __launch_bounds__(256) void smooth_l1_kernel(const float* __restrict__ x, const float* __restrict__ t, long long n, float beta,
-                                                        float* __restrict__ elem, float* __restrict__ part, const float* __restrict__ gscale,
-                                                        float* __restrict__ dx) {
-  __shared__ float red[4];
-  float acc = 0.f;
-  const float gs = gscale ? gscale[0] : 1.f;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
-    const float d = x[i] - t[i], ad = fabsf(d);
-    float l, g;
-    if (beta < 1e-5f) { l = ad; g = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
-    else if (ad < beta) { l = 0.5f * d * d / beta; g = d / beta; }
-    else { l = ad - 0.5f * beta; g = d > 0.f ? 1.f : -1.f; }
-    if (elem) elem[i] = l;
-    if (dx) dx[i] = g * gs;
-    acc += l;
+// fvcore smooth_l1_loss, one element a pair; beta < 1e-5: plain L1
+struct SmoothL1Pair {
+  static constexpr int W = 1;
+  using Lds = void;
+  static constexpr int LDS_PER_LANE = 0;
+  static __device__ __forceinline__ float pair(const float* x, const float* t, float beta, void*, bool want_grad, float* g) {
+    const float d = x[0] - t[0], ad = fabsf(d);
+    float l, gd;
+    if (beta < 1e-5f) { l = ad; gd = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f); }
+    else if (ad < beta) { l = 0.5f * d * d / beta; gd = d / beta; }
+    else { l = ad - 0.5f * beta; gd = d > 0.f ? 1.f : -1.f; }
+    if (want_grad) g[0] = gd;
+    return l;
   }
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0 && part) part[blockIdx.x] = acc;
-}
+};
 
 // ---------------------------------------------------------------------------------------------- anchor labelling
 // Matcher(thresholds=[lo,hi], labels=[l0,l1,l2], allow_low_quality_matches) over pairwise_iou(gt (G), anchors (A)) without the
@@ -500,24 +488,12 @@ extern "C" int sod_roi_align_bwd(const float* dout, const float* rois, float* dx
 
 extern "C" int sod_giou_loss_xyxy(const float* boxes1, const float* boxes2, long long P, float eps, float* elem_out, float* sum_out,
                                   const float* grad_scale, float* dboxes1, float* ws, void* stream) {
-  if (!boxes1 || !boxes2 || P < 0 || (sum_out && !ws)) return SOD_EARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = sod_nblk(P);
-  SOD_LAUNCH(giou_xyxy_kernel, dim3(g), dim3(256), 0, st, boxes1, boxes2, P, eps, elem_out, sum_out ? ws : nullptr, grad_scale, dboxes1);
-  if (sum_out) SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
+  return launch_pairs<GiouXyxyPair>(boxes1, boxes2, P, eps, elem_out, sum_out, grad_scale, dboxes1, ws, stream);
 }
 
 extern "C" int sod_smooth_l1_loss(const float* input, const float* target, long long n, float beta, float* elem_out, float* sum_out,
                                   const float* grad_scale, float* dinput, float* ws, void* stream) {
-  if (!input || !target || n < 0 || (sum_out && !ws)) return SOD_EARG;
-  hipStream_t st = (hipStream_t)stream;
-  const int g = sod_nblk(n);
-  SOD_LAUNCH(smooth_l1_kernel, dim3(g), dim3(256), 0, st, input, target, n, beta, elem_out, sum_out ? ws : nullptr, grad_scale, dinput);
-  if (sum_out) SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
+  return launch_pairs<SmoothL1Pair>(input, target, n, beta, elem_out, sum_out, grad_scale, dinput, ws, stream);
 }
 
 template <int D>

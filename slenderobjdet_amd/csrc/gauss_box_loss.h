@@ -1,6 +1,6 @@
 // The Gaussian KL-divergence loss of ONE rotated box pair (Yang et al., "Learning High-Precision Bounding Box for Rotated Object Detection
 // via Kullback-Leibler Divergence", NeurIPS 2021) and its gradient w.r.t. the first box, as device code: shared by the pair operator
-// (rotated_kld_loss.hip) and the RkldLoss policy of box_loss_policy.h (retina_box_loss.hip, rows_box_loss.hip).  The including file
+// (the RkldPair policy of rotated_kld_loss.hip) and the RkldLoss policy of box_loss_policy.h (retina_box_loss.hip, rows_box_loss.hip).  The including file
 // places this header inside its own anonymous namespace (after common.h), like rotated_iou.h.
 //
 // A box (cx, cy, w, h, angle_deg) - width axis ax = (cos t, -sin t), height axis ay = (sin t, cos t) - is the Gaussian with mean (cx, cy)

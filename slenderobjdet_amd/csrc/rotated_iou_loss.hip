@@ -1,5 +1,6 @@
 // Rotated IoU box loss: loss = 1 - IoU(pred, target) on (cx, cy, w, h, angle_deg) boxes, with its gradient w.r.t. the prediction.
-// sod_rotated_iou_loss is the pair operator (the rotated sibling of sod_giou_loss_xyxy); RotatedRetinaNet's BBOX_REG_LOSS_TYPE
+// sod_rotated_iou_loss is the pair operator (the rotated sibling of sod_giou_loss_xyxy): the RotIouPair<false> policy of the pair
+// skeleton of pair_loss.h, which owns the loop, the stores and the reduction.  RotatedRetinaNet's BBOX_REG_LOSS_TYPE
 // "rotated_iou" on the pitched delta buffer (sod_retina_riou_loss_*) is the RiouLoss policy of retina_box_loss.hip and shares the
 // gradient below (riou_grad and clip_to_slabs of box_pair_loss.h).
 // Forward: iou_rotated_lds of rotated_iou.h (detectron2's clipping, candidate points in LDS), so the IoU is the very number NMS, the
@@ -13,7 +14,7 @@
 // No dynamically indexed array: the backward pass runs in registers.  A pair whose forward IoU is 0 (disjoint boxes, a degenerate
 // area, the early-outs of rotated_iou.h) has NO gradient: five zeros.  Latency-bound fp32 work on a fraction of a percent of the
 // anchors, no MFMA.
-// sod_rotated_giou_loss is the same operator with the hull term: 1 - IoU + (C - U) / C, C the area of the convex hull of the 8 corners
+// sod_rotated_giou_loss (RotIouPair<true>) is the same operator with the hull term: 1 - IoU + (C - U) / C, C the area of the convex hull of the 8 corners
 // (rgiou_pair of box_pair_loss.h, where the method and its tie rule are written down; "rotated_giou", the RgiouLoss policy).  The IoU is
 // the same call, so the IoU part is unchanged to the bit; a pair without overlap keeps a gradient, the hull term's.
 #include "common.h"
@@ -24,57 +25,28 @@ namespace {
 
 #include "rotated_iou.h"
 #include "box_pair_loss.h"      // riou_grad, rgiou_pair
+#include "pair_loss.h"          // pair_loss_kernel, launch_pairs
 
 template <bool HULL>
-__global__ __launch_bounds__(256) void rotated_iou_loss_kernel(const float* __restrict__ b1, const float* __restrict__ b2, long long P,
-                                                               float* __restrict__ elem, float* __restrict__ part,
-                                                               const float* __restrict__ gscale, float* __restrict__ d1) {
-  __shared__ P2 rot_pts[24 * 256];      // 48 KB: the clipping's candidate points (see RotPtsLds)
-  __shared__ float red[4];
-  float acc = 0.f;
-  const float gs = gscale ? gscale[0] : 1.f;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < P; i += (long long)gridDim.x * 256) {
-    float a[5], b[5];
-#pragma unroll
-    for (int e = 0; e < 5; ++e) { a[e] = b1[i * 5 + e]; b[e] = b2[i * 5 + e]; }
-    const float iou = iou_rotated_lds(a, b, rot_pts + threadIdx.x, 256);
-    float g[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    float l;
-    if constexpr (HULL) l = d1 ? rgiou_pair<true>(a, b, iou, g) : rgiou_pair<false>(a, b, iou, nullptr);
-    else {
-      l = 1.f - iou;
-      if (d1 && iou > 0.f) riou_grad(a, b, iou, g);
-    }
-    if (elem) elem[i] = l;
-    acc += l;
-    if (d1) {
-#pragma unroll
-      for (int e = 0; e < 5; ++e) d1[i * 5 + e] = g[e] * gs;
-    }
+struct RotIouPair {
+  static constexpr int W = 5;
+  using Lds = P2;                             // the clipping's candidate points (see RotPtsLds): 48 KB a block
+  static constexpr int LDS_PER_LANE = 24;
+  static __device__ __forceinline__ float pair(const float* a, const float* b, float, P2* lds, bool want_grad, float* g) {
+    const float iou = iou_rotated_lds(a, b, lds, 256);
+    if constexpr (HULL) return want_grad ? rgiou_pair<true>(a, b, iou, g) : rgiou_pair<false>(a, b, iou, nullptr);
+    if (want_grad && iou > 0.f) riou_grad(a, b, iou, g);
+    return 1.f - iou;
   }
-  acc = block_sum_256(acc, red);
-  if (threadIdx.x == 0 && part) part[blockIdx.x] = acc;
-}
-
-template <bool HULL>
-int launch_pairs(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out, const float* grad_scale, float* dboxes1,
-                 float* ws, void* stream) {
-  if (P < 0 || (P > 0 && (!boxes1 || !boxes2)) || (sum_out && !ws)) return SOD_EARG;      // P == 0: sum_out = 0, nothing else written
-  hipStream_t st = (hipStream_t)stream;
-  const int g = sod_nblk(P);
-  SOD_LAUNCH(rotated_iou_loss_kernel<HULL>, dim3(g), dim3(256), 0, st, boxes1, boxes2, P, elem_out, sum_out ? ws : nullptr, grad_scale, dboxes1);
-  if (sum_out) SOD_LAUNCH(sod_finish_sums_kernel<>, dim3(1), dim3(256), 0, st, ws, g, 1, sum_out, 0);
-  SOD_CHECK_LAUNCH();
-  return SOD_OK;
-}
+};
 
 }  // namespace
 
 extern "C" int sod_rotated_iou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
                                     const float* grad_scale, float* dboxes1, float* ws, void* stream) {
-  return launch_pairs<false>(boxes1, boxes2, P, elem_out, sum_out, grad_scale, dboxes1, ws, stream);
+  return launch_pairs<RotIouPair<false>>(boxes1, boxes2, P, 0.f, elem_out, sum_out, grad_scale, dboxes1, ws, stream);
 }
 extern "C" int sod_rotated_giou_loss(const float* boxes1, const float* boxes2, long long P, float* elem_out, float* sum_out,
                                      const float* grad_scale, float* dboxes1, float* ws, void* stream) {
-  return launch_pairs<true>(boxes1, boxes2, P, elem_out, sum_out, grad_scale, dboxes1, ws, stream);
+  return launch_pairs<RotIouPair<true>>(boxes1, boxes2, P, 0.f, elem_out, sum_out, grad_scale, dboxes1, ws, stream);
 }

@@ -1195,23 +1195,29 @@ def roi_align_bwd(dout, rois, x_shape, spatial_scale, sampling_ratio=0, rotated=
     return dx
 
 
+def _pair_loss(name, W, a, b, params=(), want_elem=True, want_sum=True, want_grad=False, grad_scale=None):
+    """The op layer of the five pair operators (csrc/pair_loss.h): a, b of one shape - (P, W) for W > 1, any shape for W = 1 (one element
+    a pair) - -> (elem, sum (1), gradient w.r.t. a), each None unless asked for.  ``params``: the operator's float between P and elem_out."""
+    _chk(a, torch.float32, "input"); _chk(b, torch.float32, "target"); _chk(grad_scale, torch.float32, "grad_scale")
+    sh = a.shape
+    if sh != b.shape or (W > 1 and (len(sh) != 2 or sh[1] != W)):
+        raise _C.SlenderHipError(f"{name}: input and target must both be (P, {W})" if W > 1 else f"{name}: input and target must have one shape")
+    if grad_scale is not None and grad_scale.numel() < 1:
+        raise _C.SlenderHipError(f"{name}: grad_scale must hold one element")
+    dev = a.device
+    elem = torch.empty(sh if W == 1 else sh[0], dtype=torch.float32, device=dev) if want_elem else None
+    s = torch.empty(1, dtype=torch.float32, device=dev) if want_sum else None
+    d = torch.empty_like(a) if want_grad else None
+    call(name, ptr(a), ptr(b), a.numel() // W, *params, ptr(elem), ptr(s), ptr(grad_scale), ptr(d), ptr(reduce_ws(dev)) if want_sum else None, stream_ptr())
+    return elem, s, d
+
+
 def giou_loss_xyxy(b1, b2, eps=1e-7, want_grad=False, grad_scale=None):
-    _chk(b1, torch.float32, "boxes1"); _chk(b2, torch.float32, "boxes2")
-    P = b1.shape[0]
-    elem = torch.empty(P, dtype=torch.float32, device=b1.device)
-    s = torch.empty(1, dtype=torch.float32, device=b1.device)
-    d1 = torch.empty_like(b1) if want_grad else None
-    call("sod_giou_loss_xyxy", ptr(b1), ptr(b2), P, float(eps), ptr(elem), ptr(s), ptr(grad_scale), ptr(d1), ptr(reduce_ws(b1.device)), stream_ptr())
-    return elem, s, d1
+    return _pair_loss("sod_giou_loss_xyxy", 4, b1, b2, (float(eps),), want_grad=want_grad, grad_scale=grad_scale)
 
 
 def smooth_l1_loss(x, t, beta, want_grad=False, grad_scale=None):
-    _chk(x, torch.float32, "input"); _chk(t, torch.float32, "target")
-    elem = torch.empty_like(x)
-    s = torch.empty(1, dtype=torch.float32, device=x.device)
-    dx = torch.empty_like(x) if want_grad else None
-    call("sod_smooth_l1_loss", ptr(x), ptr(t), x.numel(), float(beta), ptr(elem), ptr(s), ptr(grad_scale), ptr(dx), ptr(reduce_ws(x.device)), stream_ptr())
-    return elem, s, dx
+    return _pair_loss("sod_smooth_l1_loss", 1, x, t, (float(beta),), want_grad=want_grad, grad_scale=grad_scale)
 
 
 def anchor_match(gt_boxes, anchors, thresholds, labels, allow_low_quality=True, out=None):
@@ -1483,57 +1489,37 @@ def retina_label_rotated(anchors, gt_boxes, gt_classes, gt_counts, thresholds, l
     return gt_labels, gt_deltas
 
 
-def _rotated_pair_loss_fwd(stem, pred, target, want_elem):
-    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target")
-    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
-        raise _C.SlenderHipError(f"rotated_{stem}_loss: pred and target must both be (P, 5)")
-    P = pred.shape[0]
-    elem = torch.empty(P, dtype=torch.float32, device=pred.device) if want_elem else None
-    s = torch.empty(1, dtype=torch.float32, device=pred.device)
-    call(f"sod_rotated_{stem}_loss", ptr(pred), ptr(target), P, ptr(elem), ptr(s), None, None, ptr(reduce_ws(pred.device)), stream_ptr())
-    return elem, s
-
-
-def _rotated_pair_loss_bwd(stem, pred, target, grad_scale):
-    _chk(pred, torch.float32, "pred"); _chk(target, torch.float32, "target"); _chk(grad_scale, torch.float32, "grad_scale")
-    if pred.dim() != 2 or pred.shape[1] != 5 or pred.shape != target.shape:
-        raise _C.SlenderHipError(f"rotated_{stem}_loss: pred and target must both be (P, 5)")
-    d = torch.empty_like(pred)
-    call(f"sod_rotated_{stem}_loss", ptr(pred), ptr(target), pred.shape[0], None, None, ptr(grad_scale), ptr(d), None, stream_ptr())
-    return d
-
-
 def rotated_iou_loss_fwd(pred, target, want_elem=True):
     """1 - IoU of the pairs (pred[i], target[i]) of (P, 5) boxes (cx, cy, w, h, angle_deg) -> (elem (P) or None, sum (1)); the IoU is
     box_iou_rotated's, to the bit."""
-    return _rotated_pair_loss_fwd("iou", pred, target, want_elem)
+    return _pair_loss("sod_rotated_iou_loss", 5, pred, target, want_elem=want_elem)[:2]
 
 
 def rotated_iou_loss_bwd(pred, target, grad_scale=None):
     """grad_scale[0] * d sum(1 - IoU) / d pred (P, 5), the angle's column per degree; rows without overlap (IoU exactly 0) are zero."""
-    return _rotated_pair_loss_bwd("iou", pred, target, grad_scale)
+    return _pair_loss("sod_rotated_iou_loss", 5, pred, target, want_elem=False, want_sum=False, want_grad=True, grad_scale=grad_scale)[2]
 
 
 def rotated_giou_loss_fwd(pred, target, want_elem=True):
     """1 - IoU + (C - U) / C of the pairs (pred[i], target[i]) of (P, 5) boxes, C the area of the convex hull of the 8 corners and U the
     union -> (elem (P) or None, sum (1)); the IoU is rotated_iou_loss_fwd's, to the bit."""
-    return _rotated_pair_loss_fwd("giou", pred, target, want_elem)
+    return _pair_loss("sod_rotated_giou_loss", 5, pred, target, want_elem=want_elem)[:2]
 
 
 def rotated_giou_loss_bwd(pred, target, grad_scale=None):
     """grad_scale[0] * d sum(loss) / d pred (P, 5), the angle's column per degree; rows without overlap keep the hull term's gradient."""
-    return _rotated_pair_loss_bwd("giou", pred, target, grad_scale)
+    return _pair_loss("sod_rotated_giou_loss", 5, pred, target, want_elem=False, want_sum=False, want_grad=True, grad_scale=grad_scale)[2]
 
 
 def rotated_kld_loss_fwd(pred, target, want_elem=True):
     """1 - 1 / (1 + ln(1 + KL(N_pred || N_target))) of the pairs (pred[i], target[i]) of (P, 5) boxes, each box the Gaussian with mean
     (cx, cy) and covariance R diag(w^2 / 4, h^2 / 4) R^T -> (elem (P) or None, sum (1)).  A side that is not positive or not finite: NaN."""
-    return _rotated_pair_loss_fwd("kld", pred, target, want_elem)
+    return _pair_loss("sod_rotated_kld_loss", 5, pred, target, want_elem=want_elem)[:2]
 
 
 def rotated_kld_loss_bwd(pred, target, grad_scale=None):
     """grad_scale[0] * d sum(loss) / d pred (P, 5), the angle's column per degree (exactly 0 for a square prediction or target)."""
-    return _rotated_pair_loss_bwd("kld", pred, target, grad_scale)
+    return _pair_loss("sod_rotated_kld_loss", 5, pred, target, want_elem=False, want_sum=False, want_grad=True, grad_scale=grad_scale)[2]
 
 
 def retina_decode_rotated(pred, anchors, rows, scores, A, rows_per_level, top_n, weights, scale_clamp):

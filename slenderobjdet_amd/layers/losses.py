@@ -5,6 +5,8 @@
   rotated_iou_loss          — 1 - IoU of rotated box pairs (no counterpart in the reference), csrc/rotated_iou_loss.hip
   rotated_giou_loss         — the same with the convex-hull term of GIoU, which keeps a gradient for pairs that do not overlap
   rotated_kld_loss          — the Kullback-Leibler divergence of the boxes' Gaussians (Yang et al., NeurIPS 2021), csrc/gauss_box_loss.h
+The three rotated ones are pair operators: one kernel skeleton (csrc/pair_loss.h) and one op-layer helper (functional._pair_loss), which
+they share with giou_loss_xyxy and smooth_l1_loss of layers.functional.
 """
 import torch
 from torch.autograd.function import once_differentiable

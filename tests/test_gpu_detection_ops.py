@@ -226,3 +226,96 @@ def test_anchor_match_full_size_bit_exact(cuda):
         for j in range(G):
             if best[j] > 0:
                 assert ((l_ref == 1) & (q[j] == best[j])).any()
+
+
+# ---------------------------------------------------------------------------------------------- the five pair operators: one contract
+PAIR_OPS = ["giou_xyxy", "smooth_l1[0.11]", "smooth_l1[0]", "rotated_iou", "rotated_giou", "rotated_kld"]
+PAIR_SIZES = [0, 1, 255, 257, 256 * 1024 + 1]      # the last: the smallest P at which a lane takes a second trip round the grid-stride loop
+
+
+def _pair_inputs(op, P):
+    """Seeded (a, b) on the CPU; rows 0, 1, 2 (where P has them): an identical pair, a disjoint pair, a square box."""
+    if op.startswith("smooth_l1"):
+        a, b = torch.randn(P, generator=_g(11)), torch.randn(P, generator=_g(12))
+        a[:1] = b[:1]
+        return a, b
+    if op == "giou_xyxy":
+        a, b = _boxes(P, 13), _boxes(P, 14)
+        a[:1] = b[:1]
+        if P > 1:
+            a[1] = torch.tensor([0.0, 0.0, 5.0, 5.0]); b[1] = torch.tensor([500.0, 500.0, 560.0, 560.0])
+        return a, b
+    a = _rboxes(P, 15)
+    b = a.clone()
+    b[:, :2] += (torch.rand(P, 2, generator=_g(16)) - 0.5) * 20
+    b[:, 2:4] *= 0.7 + torch.rand(P, 2, generator=_g(17)) * 0.6
+    b[:, 4] += (torch.rand(P, generator=_g(18)) - 0.5) * 40
+    b[:1] = a[:1]
+    if P > 1:
+        b[1, :2] = a[1, :2] + 1000.0
+    if P > 2:
+        a[2, 3] = a[2, 2]
+    return a, b
+
+
+def _pair_run(op, a, b, grad_scale):
+    """-> (elem, sum, gradient w.r.t. a) of one operator through its public op-layer names."""
+    from slenderobjdet_amd.layers import functional as HF
+
+    if op == "giou_xyxy":
+        return HF.giou_loss_xyxy(a, b, want_grad=True, grad_scale=grad_scale)
+    if op.startswith("smooth_l1"):
+        return HF.smooth_l1_loss(a, b, float(op[10:-1]), want_grad=True, grad_scale=grad_scale)
+    stem = op[len("rotated_"):]
+    elem, s = getattr(HF, f"rotated_{stem}_loss_fwd")(a, b)
+    return elem, s, getattr(HF, f"rotated_{stem}_loss_bwd")(a, b, grad_scale)
+
+
+def _pair_sum_roundings(P):
+    """Roundings on the longest path from an elem to sum_out, counted in csrc/pair_loss.h and csrc/common.h.  A sum that starts from 0
+    rounds once per addend after the first.  Lane loop: T = ceil(P / (256 g)) trips over g = sod_nblk(P) blocks, T - 1 roundings.
+    block_sum_256: 6 shuffle steps of wave_sum, then red[0] + red[1] + red[2] + red[3]: 6 + 3 = 9.  sod_finish_sums_kernel: a thread adds
+    ceil(g / 256) partials, ceil(g / 256) - 1 roundings, then block_sum_256 again: 9.  (P = 256 * 1024 + 1: 1 + 9 + 3 + 9 = 22.)"""
+    g = min(max((P + 255) // 256, 1), 1024)
+    trips = (P + 256 * g - 1) // (256 * g)
+    return max(trips - 1, 0) + 9 + ((g + 255) // 256 - 1) + 9
+
+
+@pytest.mark.parametrize("P", PAIR_SIZES)
+@pytest.mark.parametrize("op", PAIR_OPS)
+def test_pair_operators_one_contract(cuda, op, P):
+    """One pair per lane, so no row depends on another: the rows of a call over P pairs that a call over fewer pairs also computes - a
+    prefix of 257 and the very last row - carry the same bits there; grad_scale [0.25] scales the gradient exactly; sum_out is the
+    float64 sum of elem within the roundings of the reduction; P = 0 gives sum == 0, empty rows and no error."""
+    a, b = (t.to(cuda) for t in _pair_inputs(op, P))
+    elem, s, d = _pair_run(op, a, b, None)
+    assert elem.shape == a.shape[:1] and d.shape == a.shape and s.shape == (1,)
+    if P == 0:
+        assert s.item() == 0.0
+        return
+    assert torch.equal(_pair_run(op, a, b, torch.tensor([0.25], device=cuda))[2], d * 0.25)
+    for rows in (slice(0, min(P, 257)), slice(P - 1, P)):
+        e2, _, d2 = _pair_run(op, a[rows].contiguous(), b[rows].contiguous(), None)
+        assert torch.equal(elem[rows], e2) and torch.equal(d[rows], d2), (op, P, rows)
+    ref, mag = elem.double().sum().item(), elem.double().abs().sum().item()
+    bound = _pair_sum_roundings(P) * 2.0 ** -24 * mag
+    print(f"{op} P={P}: |sum - float64 sum| = {abs(s.item() - ref):.3e}, bound {bound:.3e}")
+    assert abs(s.item() - ref) <= bound, (op, P, s.item(), ref, bound)
+
+
+def test_pair_operators_refuse_mismatched_shapes(cuda):
+    """The op layer refuses what the kernel would misread: a second tensor with fewer rows (read out of bounds before), and for the XYXY
+    GIoU a trailing dimension other than 4."""
+    from slenderobjdet_amd import _C
+    from slenderobjdet_amd.layers import functional as HF
+
+    b1, b2 = _boxes(9, 1).to(cuda), _boxes(9, 2).to(cuda)
+    with pytest.raises(_C.SlenderHipError):
+        HF.giou_loss_xyxy(b1, b2[:8].contiguous())
+    with pytest.raises(_C.SlenderHipError):
+        HF.giou_loss_xyxy(_rboxes(9, 1).to(cuda), _rboxes(9, 2).to(cuda))
+    with pytest.raises(_C.SlenderHipError):
+        HF.giou_loss_xyxy(b1.view(-1), b2.view(-1))
+    x = torch.randn(9, generator=_g(3)).to(cuda)
+    with pytest.raises(_C.SlenderHipError):
+        HF.smooth_l1_loss(x, x[:8].contiguous(), 0.11)
