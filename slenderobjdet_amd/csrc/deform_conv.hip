@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256) void dcn_col2im_kernel(const DcnArgs a, int re
 template <int CC>
 __global__ __launch_bounds__(256) void dcn_col2im_tile_kernel(const DcnArgs a, int tiles_x, int WH, int WW, int R) {
   extern __shared__ int win[];     // [WH][WW][PS], PS = CC + 1: pixel rows start on rotating LDS banks (CC is a multiple of the bank count)
-  __shared__ float smax[4];
+  __shared__ float smax[8];
   constexpr int PS = CC + 1;
   constexpr int L = CC / 8;        // lanes per (pixel, tap)
   constexpr int PPI = 256 / L;     // pixels per pass
@@ -223,6 +223,7 @@ __global__ __launch_bounds__(256) void dcn_col2im_tile_kernel(const DcnArgs a, i
   const long long base = (long long)n * a.H * a.W;
   // pass 1: fixed-point scale of this workgroup = 2^(20 - ex) with max|d * m| < 2^ex
   float dmax = 0.f;
+  float dany = 0.f;     // max|d| alone: a tile whose MASK is zero still owes d mask = sum_c d * sample
   for (int p = pl; p < 64; p += PPI) {
     const int ho = ho0 + (p >> 3), wo = wo0 + (p & 7);
     if (ho >= a.Ho || wo >= a.Wo) continue;
@@ -236,14 +237,16 @@ __global__ __launch_bounds__(256) void dcn_col2im_tile_kernel(const DcnArgs a, i
         const float v = (float)dcv[e] * m;
         dmax = fmaxf(dmax, fabsf(v));      // fmaxf drops NaNs: they are tracked separately (a NaN gradient must stay a NaN)
         if (v != v) dmax = __builtin_inff();
+        dany = fmaxf(dany, fabsf((float)dcv[e]));
       }
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64));
-  if ((tid & 63) == 0) smax[tid >> 6] = dmax;
+  for (int o = 32; o > 0; o >>= 1) { dmax = fmaxf(dmax, __shfl_xor(dmax, o, 64)); dany = fmaxf(dany, __shfl_xor(dany, o, 64)); }
+  if ((tid & 63) == 0) { smax[tid >> 6] = dmax; smax[4 + (tid >> 6)] = dany; }
   __syncthreads();
   dmax = fmaxf(fmaxf(smax[0], smax[1]), fmaxf(smax[2], smax[3]));
+  dany = fmaxf(fmaxf(smax[4], smax[5]), fmaxf(smax[6], smax[7]));
   int ex = 0;
   (void)frexpf(dmax, &ex);
   // fixed-point quantum: a window cell receives at most 64 pixels x taps contributions of magnitude < 2^ex each, and their sum
@@ -251,7 +254,9 @@ __global__ __launch_bounds__(256) void dcn_col2im_tile_kernel(const DcnArgs a, i
   int fbits = 30;
   for (int c = 64 * taps - 1; c > 0; c >>= 1) --fbits;
   const float S = ldexpf(1.f, fbits - ex), invS = ldexpf(1.f, ex - fbits);
-  if (dmax == 0.f) return;   // all-zero gradient tile (e.g. the regression branch away from the few positive locations): nothing to add
+  // all-zero gradient tile (e.g. the regression branch away from the few positive locations): nothing to add.  The test is on the column
+  // gradients alone (a NaN has dmax = inf): with dmax == 0 from a zero mask the scatter below adds zeros to dX and still reduces d mask
+  if (dany == 0.f && dmax == 0.f) return;
   const bool finite_scale = dmax < 3.0e38f;   // inf / NaN in the tile: the float atomic path propagates them
   for (int p = pl; p < 64; p += PPI) {
     const int ho = ho0 + (p >> 3), wo = wo0 + (p & 7);
