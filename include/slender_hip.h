@@ -10,8 +10,8 @@
  *   - re-entrant per stream.  Process-wide state is limited to (a) the dynamic-LDS limit of each kernel, raised once behind an atomic
  *     flag (safe to reach from several threads), and the cached compute-unit count (the library assumes every GPU of the process is the
  *     same model; one process per GPU is the supported deployment), (b) the one table of convolution dispatch knobs, which select between
- *     kernels with identical contracts: SOD_CONV256 / SOD_CONV_PW / SOD_CONV_WS3 are read at the first dispatch and again after their
- *     setter (sod_conv_set_tile256 / _pw / _ws3) was given -1, SOD_WGRAD256 / SOD_WGRAD9 / SOD_WGRAD9_MIN_KT are read once,
+ *     kernels with identical contracts: SOD_CONV256 / SOD_CONV_PW / SOD_CONV_WS3 / SOD_CONV_TAIL / SOD_CONV_TAIL_SPLIT are read at the first
+ *     dispatch and again after their setter (sod_conv_set_tile256 / _pw / _ws3 / _tail_tile / _tail_split) was given -1, SOD_WGRAD256 / SOD_WGRAD9 / SOD_WGRAD9_MIN_KT are read once,
  *     sod_conv_set_wgrad_variant has no variable; the setters are not synchronised with launches on other threads (sod_conv_set_reverse
  *     is per calling thread), and (c) the profiling aids sod_conv_prof_* (process-wide list) / sod_conv_last_variant (per thread).
  *     Scratch memory is never cached inside the library: every entry point that needs a workspace takes it as an argument.
@@ -157,6 +157,28 @@ int sod_conv2d_wgrad_ml(int nlev, const void* const* dy, const void* const* x, f
 int sod_conv2d_dgrad_cwin(const void* dy, const void* wt_win, const void* relu_mask, void* dx,
                           int N, int H, int W, int C, int K, int R, int S, int stride, int pad, int dil, void* stream);
 int sod_conv_set_tile256(int mode);
+/* Tile of the REMAINDER launch of a split dispatch (process-wide; the few pixel tiles behind the whole rounds of the 256x256 kernel; no
+ * other launch is affected): 0 = the 128x128-family tile the ordinary rules give that remainder; 1 (default, or env SOD_CONV_TAIL) = chosen
+ * per remainder from its workgroup count, R*S*C and the CU count (the cost table in conv_dispatch.hip); a tile code = that tile for every
+ * remainder - 12812864 (128x128), 6412864 (64 output channels x 128 pixels), 6406464 (64x64), 36406464 (64x64, three LDS ring slots);
+ * -1 = re-read the env.  Every tile computes an output element with the same MFMA sequence: results are bit-identical (the float atomics
+ * of the GroupNorm statistics apart).  SOD_EARG for any other value. */
+int sod_conv_set_tail_tile(int mode);
+/* Test / measurement aid (process-wide, env SOD_CONV_TAIL_SPLIT, default 0 = off): n > 0 splits EVERY dispatch the 256x256 kernel supports
+ * that has more than n 256-pixel tiles after its first n pixel tiles, whatever the size thresholds say, so that small shapes take the
+ * main + remainder path; -1 = re-read the env. */
+int sod_conv_set_tail_split(int main_tiles);
+/* Tile code (as for sod_conv_set_tail_tile) of the remainder launch of this thread's last sod_conv2d_fwd / _dgrad dispatch, 0 if it had none. */
+int sod_conv_last_tail_variant(void);
+/* The choice sod_conv_set_tail_tile(1) makes for a remainder of tail_pixels output pixels (one level) x Nout channels, contraction Kred,
+ * on a device of cus compute units: a tile code.  Host arithmetic only. */
+int sod_conv_tail_tile_select(long long tail_pixels, int Nout, int Kred, int cus);
+/* Which kernels a forward (mode 0) / data-gradient (mode 1) dispatch of this geometry (H, W: the convolution's INPUT side, as for
+ * sod_conv2d_fwd_ml / _dgrad_ml; no epilogue operands, bf16 output) would run on a device of the cached CU count (256 when there is no
+ * device), without launching anything: returns the sod_conv_last_variant code (< 0: SOD_EARG / SOD_ESIZE), *tail_variant (optional) the
+ * remainder's tile code or 0, *main_pt_tiles (optional) the 256-pixel tiles of the main launch of a split dispatch or 0. */
+int sod_conv_plan(int mode, int nlev, int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
+                  int* tail_variant, int* main_pt_tiles);
 /* Process-wide: 1 (default; -1 = re-read SOD_CONV_PW) sends the EXPANDING 1x1 convolutions of the bottleneck blocks and their data gradients
  * (C in {128, 256, 512} -> 4 / 8 / 16 x 128 channels, stride 1, one dense level, >= 16384 pixels, 256-CU device; forward epilogues bias /
  * shortcut / ReLU / bit mask, backward accumulate / bit mask) to the persistent weight-stationary kernel of conv_pw.hip; 0 keeps them on
@@ -190,6 +212,10 @@ int sod_conv_last_variant(void);
  * in call order, clears the list and returns the count (capacity 8192). */
 int sod_conv_prof_enable(int on);
 int sod_conv_prof_collect(float* ms, int* variant, float* frac, int* mode, int max);
+/* sod_conv_prof_enable(2) also records a hipEvent pair around the REMAINDER launch of every split dispatch (tools/bench_conv_tails.py);
+ * sod_conv_prof_collect_tails, called BEFORE sod_conv_prof_collect (which clears the list), writes for the same rows the remainder
+ * launch's duration (ms; 0 where there was none or it was not timed) and tile code (0 = none) and returns the row count. */
+int sod_conv_prof_collect_tails(float* tail_ms, int* tail_variant, int max);
 
 /* ---------------------------------------------------------------------------------------------------------
  * GroupNorm (+ fused ReLU), NHWC bf16 — nn.GroupNorm(32, C) + nn.ReLU in FCOSHead (fcosv2.py:315-336).

@@ -50,6 +50,12 @@ _SIGS = {
     "sod_upsample2x_bwd": [_P, _P, _I, _I, _I, _I, _P],
     "sod_conv2d_dgrad_cwin": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "sod_conv_set_tile256": [_I],
+    "sod_conv_set_tail_tile": [_I],
+    "sod_conv_set_tail_split": [_I],
+    "sod_conv_last_tail_variant": [],
+    "sod_conv_tail_tile_select": [_L, _I, _I, _I],
+    "sod_conv_plan": [_I, _I, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P],
+    "sod_conv_prof_collect_tails": [_P, _P, _I],
     "sod_conv_set_pw": [_I],
     "sod_conv_set_ws3": [_I],
     "sod_conv_set_wgrad_variant": [_I],

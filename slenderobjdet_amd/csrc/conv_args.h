@@ -110,7 +110,30 @@ __device__ __forceinline__ void gn_acc_finish(GnAcc& g, uint32_t pa, uint32_t pb
 // conv_igemm.hip: the 128x128-family kernel.  Tile = BQ output channels x BP pixels per workgroup, 64 contraction elements per K-step
 // (_K32: 32, linear path only); `generic` = the per-chunk gather path for channel counts that are no multiple of 64.  *variant receives
 // BQ * 100000 + BP * 100 + BK + generic (sod_conv_last_variant).
-enum ConvTile { TILE_16x256, TILE_64x256, TILE_64x256_K32, TILE_128x128, TILE_128x128_K32 };
+// TILE_64x64 / TILE_64x128 / TILE_64x64_R3 (three LDS ring slots) are the remainder tiles of a split dispatch (dispatch_conv: the few pixel
+// tiles behind the whole rounds of the 256x256 kernel), linear path only: the same MFMA instruction and K order per output element as
+// TILE_128x128, i.e. bit-identical results, with a shorter K-step per workgroup.
+enum ConvTile { TILE_16x256, TILE_64x256, TILE_64x256_K32, TILE_128x128, TILE_128x128_K32, TILE_64x64, TILE_64x128, TILE_64x64_R3, TILE_COUNT };
+struct ConvTileShape { int BQ, BP, BK, nstage; };
+inline ConvTileShape conv_tile_shape(ConvTile t) {
+  switch (t) {
+    case TILE_16x256: return {16, 256, 64, 2};
+    case TILE_64x256: return {64, 256, 64, 2};
+    case TILE_64x256_K32: return {64, 256, 32, 2};
+    case TILE_128x128: return {128, 128, 64, 2};
+    case TILE_128x128_K32: return {128, 128, 32, 2};
+    case TILE_64x64: return {64, 64, 64, 2};
+    case TILE_64x128: return {64, 128, 64, 2};
+    case TILE_64x64_R3: return {64, 64, 64, 3};
+    default: return {0, 0, 0, 0};
+  }
+}
+// the code launch_conv128 reports in *variant; + 10000000 * ring slots for the ring forms (sod_conv_set_tail_tile / sod_conv_last_tail_variant)
+inline int conv_tile_code(ConvTile t, bool generic) {
+  const ConvTileShape s = conv_tile_shape(t);
+  return s.BQ * 100000 + s.BP * 100 + s.BK + (generic ? 1 : 0);
+}
+inline int conv_tail_tile_code(ConvTile t) { const ConvTileShape s = conv_tile_shape(t); return conv_tile_code(t, false) + (s.nstage > 2 ? 10000000 * s.nstage : 0); }
 int launch_conv128(const ConvArgs& a, int mode, bool out_f32, ConvTile tile, bool generic, hipStream_t st, int* variant);
 
 // conv_igemm256.hip: 256x256x64 tile, 8 waves, 8-phase main loop.  Returns SOD_EARG when the shape is outside its fast path.

@@ -20,6 +20,9 @@ int device_cus() {
 namespace {
 
 thread_local int g_last_variant = 0;   // kernel variant chosen by the last forward / data-gradient dispatch (sod_conv_last_variant)
+thread_local int g_last_tail = 0;      // tile code of that dispatch's remainder launch, 0 = none (sod_conv_last_tail_variant)
+thread_local bool g_plan_only = false; // sod_conv_plan: walk the dispatch rules, launch nothing
+thread_local int g_plan_main_pt = 0;   // sod_conv_plan: 256-pixel tiles of the main launch of a split dispatch
 thread_local int g_conv_reverse = 0;   // sod_conv_set_reverse: per calling thread (the forward thread and autograd's worker each bracket their own launches)
 
 // Every dispatch knob.  Process-wide; the setters of the C ABI write the same fields.
@@ -27,6 +30,9 @@ struct ConvKnobs {
   int conv256 = -1;         // SOD_CONV256 (default 1), sod_conv_set_tile256: 0 off; 1 heuristic; 2 every supported shape; -1: re-read at the next dispatch
   int pw = -1;              // SOD_CONV_PW (default 1), sod_conv_set_pw: 0 off; 1 on; -1: re-read at the next dispatch
   int ws3 = -1;             // SOD_CONV_WS3 (default 1), sod_conv_set_ws3: 0 off; 1 large launches; 2 every supported shape; -1: re-read at the next dispatch
+  int tail = -1;            // SOD_CONV_TAIL (default 1), sod_conv_set_tail_tile: remainder launch of a split dispatch - 0 the ordinary rules' tile; 1 tail_tile_for(); else a forced
+                            // tile code; -1: re-read at the next dispatch
+  int tail_split = -1;      // SOD_CONV_TAIL_SPLIT (default 0), sod_conv_set_tail_split: > 0 splits every 256-capable dispatch after that many pixel tiles (tests, tools)
   int wgrad256 = 1;         // SOD_WGRAD256, read once: 0 never; 1 per-shape rule; 2 every supported shape
   int wgrad9 = 1;           // SOD_WGRAD9, read once: likewise
   int wgrad9_min_kt = 24;   // SOD_WGRAD9_MIN_KT, read once
@@ -44,6 +50,8 @@ ConvKnobs& knobs() {
   if (k.conv256 < 0) k.conv256 = env("SOD_CONV256", 1);
   if (k.pw < 0) k.pw = env("SOD_CONV_PW", 1);
   if (k.ws3 < 0) k.ws3 = env("SOD_CONV_WS3", 1);
+  if (k.tail < 0) k.tail = env("SOD_CONV_TAIL", 1);
+  if (k.tail_split < 0) k.tail_split = env("SOD_CONV_TAIL_SPLIT", 0);
   return k;
 }
 
@@ -57,17 +65,24 @@ struct ConvProf {
   int* variant = nullptr;
   int* mode = nullptr;
   float* frac = nullptr;
+  hipEvent_t* tail_ev = nullptr;      // sod_conv_prof_enable(2): a second pair per row around the remainder launch of a split dispatch
+  int* tail_variant = nullptr;        // 0 = the row's dispatch had no remainder launch
+  char* tail_timed = nullptr;
   int cap = 0;
   std::atomic<int> n{0};
   std::atomic<int> on{0};
 };
 ConvProf g_prof;
 thread_local int g_prof_depth = 0;
+thread_local int g_prof_row = -1;     // row of this thread's last top-level dispatch (-1: not recorded)
 inline int prof_begin(hipStream_t st) {
   ConvProf& p = g_prof;
-  if (!p.on.load(std::memory_order_relaxed) || g_prof_depth) return -1;
+  if (!p.on.load(std::memory_order_relaxed) || g_prof_depth || g_plan_only) return -1;
+  g_prof_row = -1;
   const int i = p.n.fetch_add(1);
   if (i >= p.cap) { p.n.store(p.cap); return -1; }
+  g_prof_row = i;
+  p.tail_variant[i] = 0; p.tail_timed[i] = 0;
   (void)hipEventRecord(p.ev[2 * i], st);
   return i;
 }
@@ -86,11 +101,59 @@ int timed(hipStream_t st, const int& variant, float frac, int mode, F launch) {
   return rc;
 }
 
+// ---- the remainder launch of a split dispatch ----
+// A remainder of a few 256-pixel tiles leaves most CUs empty, so its launch lasts as long as ONE workgroup's K loop (or a few, where
+// several share a CU): a smaller tile has fewer MFMAs and fragment reads per K-step, a deeper LDS ring hides more of the load latency of
+// a lone workgroup, and the loop is shorter.  With k workgroups resident per CU one round of a launch measured us_fixed[k - 1] +
+// K-steps * us_step[k - 1] microseconds (K-steps of 64; launch to end, so the fixed part holds the launch itself, prologue and epilogue).
+// estimate = whole rounds of max_per_cu workgroups per CU + the last round with k = ceil(workgroups left / CUs); the smallest estimate wins, and a tile
+// must beat the 128x128 tile by 5 % to replace it.
+// Constants: tools/bench_conv_tails.py --calibrate on one MI355X, 2026-10-20 (profiles/conv_tails_before.txt, "calibration": the forward
+// rows at 36 and 16 K-steps solved for the two terms; k from the rows whose workgroup count gives that k).
+struct TailTileCost {
+  ConvTile tile;
+  int max_per_cu;
+  float us_fixed[4], us_step[4];
+};
+constexpr TailTileCost kTailTiles[] = {
+    {TILE_128x128, 2, {10.1f, 11.6f, 0.f, 0.f}, {0.590f, 0.815f, 0.f, 0.f}},
+    {TILE_64x128, 3, {7.9f, 8.8f, 9.4f, 0.f}, {0.545f, 0.558f, 0.850f, 0.f}},
+    {TILE_64x64, 4, {6.1f, 6.6f, 7.5f, 8.2f}, {0.473f, 0.478f, 0.485f, 0.630f}},
+    {TILE_64x64_R3, 3, {5.8f, 6.2f, 6.8f, 0.f}, {0.338f, 0.393f, 0.565f, 0.f}},
+};
+bool tail_tile_from_code(int code, ConvTile* tile) {
+  for (const TailTileCost& c : kTailTiles)
+    if (conv_tail_tile_code(c.tile) == code) { *tile = c.tile; return true; }
+  return false;
+}
+// lev_pixels: the pixels each level leaves to the remainder launch
+ConvTile tail_tile_for(const long long* lev_pixels, int nlev, int Nout, int Kred, int cus) {
+  ConvTile best = TILE_128x128;
+  double best_us = 0.0;
+  const int steps = (Kred + 63) / 64;
+  for (const TailTileCost& c : kTailTiles) {
+    const ConvTileShape s = conv_tile_shape(c.tile);
+    long long blocks = 0;
+    for (int l = 0; l < nlev; ++l) blocks += (lev_pixels[l] + s.BP - 1) / s.BP;
+    blocks *= (Nout + s.BQ - 1) / s.BQ;
+    if (blocks <= 0) return TILE_128x128;
+    const auto round_us = [&](long long k) { return (double)c.us_fixed[k - 1] + steps * (double)c.us_step[k - 1]; };
+    const long long per_round = (long long)c.max_per_cu * cus, left = blocks % per_round;
+    const double us = (double)(blocks / per_round) * round_us(c.max_per_cu) + (left ? round_us((left + cus - 1) / cus) : 0.0);
+    if (c.tile == TILE_128x128) best_us = us * 0.95;
+    else if (us < best_us) { best = c.tile; best_us = us; }
+  }
+  return best;
+}
+
 int dispatch_conv(const ConvArgs& a, int mode, bool out_f32, hipStream_t st) {
   const bool generic = (a.Cred & 63) != 0 || a.R * a.S > 64;      // the linear path keeps one validity bit per tap in 64-bit masks
-  const auto conv128 = [&](ConvTile tile) {
-    return timed(st, g_last_variant, 1.f, mode, [&] { return launch_conv128(a, mode, out_f32, tile, generic, st, &g_last_variant); });
+  const auto conv128_of = [&](const ConvArgs& args, ConvTile tile) {
+    if (g_plan_only) { g_last_variant = conv_tile_code(tile, generic); return (int)SOD_OK; }
+    return timed(st, g_last_variant, 1.f, mode, [&] { return launch_conv128(args, mode, out_f32, tile, generic, st, &g_last_variant); });
   };
+  const auto conv128 = [&](ConvTile tile) { return conv128_of(a, tile); };
+  if (!g_prof_depth) { g_last_tail = 0; g_plan_main_pt = 0; }
   if (a.cwin) {         // channel window: the window IS the 128-row q-tile of this variant; Cred = 128 -> never generic
     if (generic || a.nlev != 1 || (a.Nout & 127)) return SOD_EARG;
     return conv128(TILE_128x128);
@@ -100,11 +163,13 @@ int dispatch_conv(const ConvArgs& a, int mode, bool out_f32, hipStream_t st) {
   // persistent weight-stationary kernel (conv_pw.hip) for the expanding 1x1 convolutions; SOD_CONV_PW=0 / sod_conv_set_pw(0) disables it
   if (k.pw && pw_supported(a, mode, out_f32, cus)) {
     g_last_variant = 7001;
+    if (g_plan_only) return SOD_OK;
     return timed(st, 7001, 1.f, mode, [&] { return launch_pw(a, mode, st); });
   }
   // persistent weight-stationary 3x3 kernel (conv_ws3.hip) for the 128 -> 128 convolutions of res3; SOD_CONV_WS3=0 disables it
   if (k.ws3 && ws3_supported(a, mode, out_f32, cus, k.ws3 == 2)) {
     g_last_variant = 7003;
+    if (g_plan_only) return SOD_OK;
     return timed(st, 7003, 1.f, mode, [&] { return launch_ws3(a, mode, st); });
   }
   // 256x256 8-phase kernel (conv_igemm256.hip) for the large compute-bound shapes.  SOD_CONV256=0 disables it, =2 forces it for
@@ -121,8 +186,49 @@ int dispatch_conv(const ConvArgs& a, int mode, bool out_f32, hipStream_t st) {
     const long long b256 = pt256 * nq;
     const auto conv256 = [&](int max_pt_tiles, float frac) {
       g_last_variant = 256;
+      if (g_plan_only) return (int)SOD_OK;
       return timed(st, 256, frac, mode, [&] { return launch_conv256(a, mode, out_f32, max_pt_tiles, st); });
     };
+    // The first main_pt pixel tiles on the 256 kernel, the rest in a remainder launch of the 128x128-family kernel (knobs().tail).
+    const auto split_after = [&](int main_pt) {
+      long long ptot = 0;
+      for (int l = 0; l < a.nlev; ++l) ptot += a.lev[l].P;
+      g_plan_main_pt = main_pt;
+      int rc = conv256(main_pt, (float)((double)main_pt * 256.0 / (double)ptot));     // main tiles are full 256-pixel tiles
+      if (rc) return rc;
+      ConvArgs tail = a;
+      long long left[MAXLEV];
+      for (int l = 0; l < tail.nlev; ++l) {
+        const int tl = (tail.lev[l].P + 255) / 256;
+        if (main_pt >= tl) { tail.lev[l].pstart = tail.lev[l].P; main_pt -= tl; }
+        else { tail.lev[l].pstart = main_pt * 256; main_pt = 0; }
+        left[l] = tail.lev[l].P - tail.lev[l].pstart;
+      }
+      ConvTile tile = TILE_128x128;
+      if (k.tail == 1) tile = tail_tile_for(left, tail.nlev, a.Nout, a.Kred, cus);
+      else if (k.tail != 0 && !tail_tile_from_code(k.tail, &tile)) return (int)SOD_EARG;
+      // the remainder launch belongs to this dispatch: no profile row of its own; sod_conv_prof_enable(2) times it in the main launch's row
+      ConvProf& p = g_prof;
+      const int row = (!g_plan_only && !g_prof_depth && p.on.load(std::memory_order_relaxed) == 2) ? g_prof_row : -1;
+      if (row >= 0) (void)hipEventRecord(p.tail_ev[2 * row], st);
+      ++g_prof_depth;
+      if (k.tail == 0 || (k.tail == 1 && tile == TILE_128x128)) {      // the ordinary rules' tile (128x128, or its BK = 32 form for long remainders)
+        rc = dispatch_conv(tail, mode, out_f32, st);
+        g_last_tail = g_last_variant;
+      } else {
+        rc = conv128_of(tail, tile);
+        g_last_tail = conv_tail_tile_code(tile);
+      }
+      --g_prof_depth;
+      if (row >= 0) {
+        (void)hipEventRecord(p.tail_ev[2 * row + 1], st);
+        p.tail_timed[row] = 1;
+      }
+      if (!g_plan_only && !g_prof_depth && g_prof_row >= 0 && p.on.load(std::memory_order_relaxed)) p.tail_variant[g_prof_row] = g_last_tail;
+      g_last_variant = 256;      // whole rounds on the 256 kernel (+ a short remainder launch)
+      return rc;
+    };
+    if (k.tail_split > 0 && pt256 > k.tail_split) return split_after(k.tail_split);      // tests, tools/bench_conv_tails.py
     if (k.conv256 == 2) return conv256(0, 1.f);
     // (thresholds swept in rounds 2 - 4, DESIGN.md section 4: contraction >= 1024 - 512 / 256 measured 587-588 / 575 vs 593 img/s -, at
     // least one full round of tiles, output-channel counts that are no multiple of 256 - RetinaNet's 720 class scores: the third q-tile
@@ -138,22 +244,7 @@ int dispatch_conv(const ConvArgs& a, int mode, bool out_f32, hipStream_t st) {
       // 12 / 5 % of a round split off: 633.2 / 631.7 / 634.6 / 631.0 img/s, three alternating 100-step runs each - no difference.
       const long long full = b256 / cus * cus, rem = b256 - full;
       if (rem == 0 || rem * 2 >= (long long)cus || (full / nq) * nq != full) return conv256(0, 1.f);
-      int main_pt = (int)(full / nq);
-      long long ptot = 0;
-      for (int l = 0; l < a.nlev; ++l) ptot += a.lev[l].P;
-      int rc = conv256(main_pt, (float)((double)main_pt * 256.0 / (double)ptot));     // main tiles are full 256-pixel tiles
-      if (rc) return rc;
-      ConvArgs tail = a;
-      for (int l = 0; l < tail.nlev; ++l) {
-        const int tl = (tail.lev[l].P + 255) / 256;
-        if (main_pt >= tl) { tail.lev[l].pstart = tail.lev[l].P; main_pt -= tl; }
-        else { tail.lev[l].pstart = main_pt * 256; main_pt = 0; }
-      }
-      ++g_prof_depth;            // the tail launch belongs to this dispatch: no event pair of its own
-      rc = dispatch_conv(tail, mode, out_f32, st);
-      --g_prof_depth;
-      g_last_variant = 256;      // whole rounds on the 256 kernel (+ a short 128x128 tail launch)
-      return rc;
+      return split_after((int)(full / nq));
     }
   }
   // (Round 6 measured an 80(q) x 256(p) tile - one wave row of 5 x 4 MFMA blocks, BK = 32, three workgroups per CU - for the 80 class scores
@@ -591,6 +682,31 @@ extern "C" int sod_conv2d_wgrad_ml(int nlev, const void* const* dy, const void* 
 
 extern "C" int sod_conv_last_variant(void) { return g_last_variant; }
 
+extern "C" int sod_conv_last_tail_variant(void) { return g_last_tail; }
+
+extern "C" int sod_conv_tail_tile_select(long long tail_pixels, int Nout, int Kred, int cus) {
+  if (tail_pixels <= 0 || Nout <= 0 || Kred <= 0 || cus <= 0) return SOD_EARG;
+  return conv_tail_tile_code(tail_tile_for(&tail_pixels, 1, Nout, Kred, cus));
+}
+
+extern "C" int sod_conv_plan(int mode, int nlev, int N, const int* H, const int* W, int C, int K, int R, int S, int stride, int pad, int dil,
+                             int* tail_variant, int* main_pt_tiles) {
+  if (!H || !W || nlev <= 0 || nlev > MAXLEV || (mode != MODE_FWD && mode != MODE_DGRAD)) return SOD_EARG;
+  void* const dummy = (void*)(uintptr_t)256;      // never dereferenced: nothing is launched
+  const void* src[MAXLEV];
+  void* dst[MAXLEV];
+  for (int l = 0; l < nlev; ++l) { src[l] = dummy; dst[l] = dummy; }
+  const Geo g{N, H, W, C, K, R, S, stride, pad, dil};
+  g_plan_only = true;
+  const int rc = mode == MODE_FWD ? conv_fwd(nlev, src, dummy, nullptr, dst, g, 0, 0, 0, FwdExtra{}, nullptr)
+                                  : conv_dgrad(nlev, src, dummy, dst, g, 0, DgradExtra{}, nullptr);
+  g_plan_only = false;
+  if (rc) return rc < 0 ? rc : SOD_EARG;
+  if (tail_variant) *tail_variant = g_last_tail;
+  if (main_pt_tiles) *main_pt_tiles = g_plan_main_pt;
+  return g_last_variant;
+}
+
 extern "C" int sod_conv_prof_enable(int on) {
   ConvProf& p = g_prof;
   if (on && !p.ev) {
@@ -599,13 +715,38 @@ extern "C" int sod_conv_prof_enable(int on) {
     p.variant = (int*)malloc(sizeof(int) * CAP);
     p.mode = (int*)malloc(sizeof(int) * CAP);
     p.frac = (float*)malloc(sizeof(float) * CAP);
-    if (!p.ev || !p.variant || !p.mode || !p.frac) return SOD_EARG;
+    p.tail_variant = (int*)malloc(sizeof(int) * CAP);
+    p.tail_timed = (char*)malloc(CAP);
+    if (!p.ev || !p.variant || !p.mode || !p.frac || !p.tail_variant || !p.tail_timed) return SOD_EARG;
     for (int i = 0; i < 2 * CAP; ++i)
       if (hipEventCreate(&p.ev[i]) != hipSuccess) return SOD_EARG;
     p.cap = CAP;
   }
-  p.on.store(on ? 1 : 0);
+  if (on == 2 && !p.tail_ev) {      // the remainder launches' own event pairs: only for the tool that asks for them
+    hipEvent_t* ev = (hipEvent_t*)malloc(sizeof(hipEvent_t) * 2 * p.cap);
+    if (!ev) return SOD_EARG;
+    for (int i = 0; i < 2 * p.cap; ++i)
+      if (hipEventCreate(&ev[i]) != hipSuccess) return SOD_EARG;
+    p.tail_ev = ev;
+  }
+  p.on.store(on == 2 ? 2 : on ? 1 : 0);
   return SOD_OK;
+}
+
+extern "C" int sod_conv_prof_collect_tails(float* tail_ms, int* tail_variant, int max) {
+  ConvProf& p = g_prof;
+  const int have = p.n.load();
+  const int n = have < max ? have : max;
+  if (n > 0 && (!tail_ms || !tail_variant)) return SOD_EARG;
+  for (int i = 0; i < n; ++i) {
+    float t = 0.f;
+    if (p.tail_timed[i] && p.tail_ev) {
+      if (hipEventSynchronize(p.tail_ev[2 * i + 1]) != hipSuccess) return SOD_EARG;
+      if (hipEventElapsedTime(&t, p.tail_ev[2 * i], p.tail_ev[2 * i + 1]) != hipSuccess) return SOD_EARG;
+    }
+    tail_ms[i] = t; tail_variant[i] = p.tail_variant[i];
+  }
+  return n;
 }
 
 extern "C" int sod_conv_prof_collect(float* ms, int* variant, float* frac, int* mode, int max) {
@@ -644,6 +785,19 @@ extern "C" int sod_conv_set_ws3(int mode) {
 extern "C" int sod_conv_set_pw(int on) {
   if (on < -1 || on > 1) return SOD_EARG;
   knobs().pw = on;
+  return SOD_OK;
+}
+
+extern "C" int sod_conv_set_tail_tile(int mode) {
+  ConvTile t;
+  if (mode < -1 || (mode > 1 && !tail_tile_from_code(mode, &t))) return SOD_EARG;
+  knobs().tail = mode;
+  return SOD_OK;
+}
+
+extern "C" int sod_conv_set_tail_split(int main_tiles) {
+  if (main_tiles < -1) return SOD_EARG;
+  knobs().tail_split = main_tiles;
   return SOD_OK;
 }
 

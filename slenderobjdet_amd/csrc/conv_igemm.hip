@@ -854,6 +854,14 @@ int launch_tile(const ConvArgs& a, ConvTile tile, bool generic, hipStream_t st, 
       return generic ? SOD_EARG : launch_conv<MODE, false, 1, 4, 4, 4, OUT_F32, 32>(a, st, variant);
     case TILE_128x128_K32:
       return generic ? SOD_EARG : launch_conv<MODE, false, 2, 2, 4, 4, OUT_F32, 32>(a, st, variant);
+    // remainder tiles of a split dispatch (conv_dispatch.hip): 2 x 2 waves of 2 x 2 / 2 x 4 MFMA blocks, 64-deep K-steps
+    case TILE_64x64:
+      return generic ? SOD_EARG : launch_conv<MODE, false, 2, 2, 2, 2, OUT_F32>(a, st, variant);
+    case TILE_64x128:
+      return generic ? SOD_EARG : launch_conv<MODE, false, 2, 2, 2, 4, OUT_F32>(a, st, variant);
+    case TILE_64x64_R3:
+      return generic ? SOD_EARG : launch_conv<MODE, false, 2, 2, 2, 2, OUT_F32, 64, 3>(a, st, variant);
+    case TILE_COUNT: break;
   }
   return SOD_EARG;
 }
