@@ -15,6 +15,8 @@ import numpy as np
 import torch
 import torch.distributed as dist
 
+from . import grad_sched as GS
+
 _ALIGN = 64  # elements; keeps every tensor 256-B aligned
 
 
@@ -146,9 +148,9 @@ class ParamArena:
 
     def zero_grad(self):
         if self.device.type == "cuda":
-            from . import functional as HF
-            HF.drop_held()           # (launches parked by a backward pass that died: not into the fresh arena)
-            HF.wgrad_join()          # never clear the arena under weight-gradient kernels still running on the side stream
+            # never clear the arena under weight-gradient kernels still running on the side stream (launches parked by a backward pass
+            # that died are dropped: not into the fresh arena)
+            GS.join()
         self.grads.zero_()
 
     def bump(self):
@@ -198,9 +200,8 @@ class ParamArena:
         if self._pending is None:
             return
         if self.device.type == "cuda":
-            from . import functional as HF
             # behind the launches an open wgrad_batch has collected: the bucket must not reach the reducer before they are issued
-            HF.batch_or_call(lambda: self._mark_ready_now(p))
+            GS.batch_or_call(lambda: self._mark_ready_now(p))
         else:
             self._mark_ready_now(p)
 
@@ -218,7 +219,7 @@ class ParamArena:
             ev = torch.cuda.Event()
             ev.record(torch.cuda.current_stream())
             from . import functional as HF
-            sides = HF.wgrad_side_streams(self.device)
+            sides = GS.wgrad_side_streams(self.device)
             with torch.cuda.stream(self._comm_stream):
                 self._comm_stream.wait_event(ev)
                 # A 32 MB bucket mixes gradients produced on different streams (GroupNorm dgamma / dbeta and bias gradients on the main
@@ -230,7 +231,7 @@ class ParamArena:
                     self._comm_stream.wait_stream(main)
                 for side in sides:          # weight gradients of this bucket were enqueued on the wgrad side stream(s)
                     self._comm_stream.wait_stream(side)
-                for aux in HF.aux_compute_streams(self.device):   # a bucket may mix parameters whose backward nodes ran on different
+                for aux in GS.aux_compute_streams(self.device):   # a bucket may mix parameters whose backward nodes ran on different
                     self._comm_stream.wait_stream(aux)            # streams (the FCOS box tower has its own)
                 wire = view if self.bucket_dtype == torch.float32 else view.to(self.bucket_dtype)
                 h = self._reduce(wire)
@@ -266,8 +267,7 @@ class ParamArena:
         if self._pending is None:
             return
         if self.device.type == "cuda":
-            from . import functional as HF
-            HF.wgrad_join()
+            GS.join()
         for bi in range(len(self.buckets)):
             if not self._launched[bi]:
                 self._launch_bucket(bi)

@@ -159,20 +159,14 @@ class _DeformConvFn(torch.autograd.Function):
             grouped = getattr(mod, "groups", 1) > 1
             # groups > 1: dW of the dense embedding into a scratch tensor on the CURRENT stream, its diagonal blocks added to the arena gradient
             dw = torch.zeros((K, 1, 1, k * k * C), dtype=torch.float32, device=dy.device) if grouped else arena.grad_view(mod.weight).view(K, 1, 1, k * k * C)
-            prev_side = HF.WGRAD_SIDE_STREAM
-            if grouped:
-                HF.WGRAD_SIDE_STREAM = False
-            try:
-                if ctx.fused:
-                    HF.deform_conv_wgrad_fused(dy, x, offset, mask, dw, (k, k), mod.stride, mod.padding, mod.dilation, dg, off_ld, mask_ld, mask_is_logit,
-                                               qscale=mod.bn_scale)
-                else:
-                    if cols is None:
-                        cols = HF.deform_im2col(x, offset, mask, (k, k), mod.stride, mod.padding, mod.dilation, dg, off_ld, mask_ld, mask_is_logit)
-                    HF.conv2d_wgrad(dy, cols, dw, 1, 1, 1, 0, 1, qscale=mod.bn_scale)
-                    del cols
-            finally:
-                HF.WGRAD_SIDE_STREAM = prev_side
+            if ctx.fused:
+                HF.deform_conv_wgrad_fused(dy, x, offset, mask, dw, (k, k), mod.stride, mod.padding, mod.dilation, dg, off_ld, mask_ld, mask_is_logit,
+                                           qscale=mod.bn_scale, side=not grouped)
+            else:
+                if cols is None:
+                    cols = HF.deform_im2col(x, offset, mask, (k, k), mod.stride, mod.padding, mod.dilation, dg, off_ld, mask_ld, mask_is_logit)
+                HF.conv2d_wgrad(dy, cols, dw, 1, 1, 1, 0, 1, qscale=mod.bn_scale, side=not grouped)
+                del cols
             if grouped:
                 arena.grad_view(mod.weight).add_(mod.blocks_of(dw.view(K, k, k, C)))
             arena.mark_ready(mod.weight)

@@ -10,6 +10,8 @@ import torch
 
 from .. import _C
 from .._C import call, ptr, stream_ptr
+from . import grad_sched as GS
+from .grad_sched import make_stream, join as wgrad_join      # for callers outside the package (bench.py, tools, tests)
 
 IOU_TYPES = {"iou": 0, "linear_iou": 1, "giou": 2}
 
@@ -92,222 +94,18 @@ def _prof_end(kind, flops, e0, desc=None, stream=None):
     PROFILE.append((kind, flops, e0, e1, desc, variant))
 
 
-# Weight gradients have no consumer until the optimizer (or the bucket all-reduce), while the data gradient of the same layer is on
-# the critical path of backward.  Inside an autograd backward pass the wgrad launches therefore go to a per-device SIDE stream:
-# the hardware interleaves the two queues, so the tail of one kernel's grid is filled by the other's workgroups.  The main stream
-# joins the side stream in an end-of-backward callback (and the all-reduce stream waits for it per bucket, arena._launch_bucket).
-# SOD_WGRAD_STREAM=0 keeps everything on one stream.
+# Inside an autograd backward pass the weight- / bias-gradient launches go to the side stream of layers/grad_sched.py, which owns every
+# stream, batch and parking decision of backward.  SOD_WGRAD_STREAM=0: all on one stream; read at launch time (bench.py switches it).
 WGRAD_SIDE_STREAM = os.environ.get("SOD_WGRAD_STREAM", "1") != "0"
-_side_streams = {}
-_side_keep = []
-_side_join_queued = False
 
 
-_aux_streams = {}
+def _side_launch(out, tensors, launch, side=True):
+    """Issue ``launch(stream)`` behind the open wgrad_batch if there is one, else now; -> ``out``.  ``stream``: the scheduler's side stream
+    (it keeps the operands ``tensors`` alive until the join), or None = the current one (``side=False``, flag off, outside a backward)."""
+    GS.batch_or_call(lambda: launch(GS.side_stream(out.device, tensors) if WGRAD_SIDE_STREAM and side else None))
+    return out
 
 
-def cu_mask_words(lo, hi, total=256):
-    """Bit mask (list of 32-bit words) selecting the logical CUs lo .. hi-1 of hipExtStreamCreateWithCUMask's numbering.  On MI355X bit i
-    lies on XCD i % 8, so a range whose ends are multiples of 8 takes the same number of CUs from every XCD (the workgroup -> XCD
-    round-robin of a launch then still meets equally wide XCDs)."""
-    words = [0] * ((total + 31) // 32)
-    for i in range(max(0, lo), min(hi, total)):
-        words[i // 32] |= 1 << (i % 32)
-    return words
-
-
-def make_stream(device, priority=0, role=None):
-    """A side stream of the training step.  ``SOD_CUMASK_<ROLE>=lo:hi`` (role = WGRAD / TOWER / PREFETCH / MAIN) confines it to the
-    logical compute units lo .. hi-1 (sod_stream_create_cumask; such a stream has the default priority); without the variable it is a
-    plain torch stream of the given HIP priority."""
-    spec = os.environ.get(f"SOD_CUMASK_{role}") if role else None
-    if not spec:
-        return torch.cuda.Stream(device=device, priority=priority)
-    lo, hi = (int(v) for v in spec.split(":"))
-    words = cu_mask_words(lo, hi)
-    arr = (ctypes.c_uint * len(words))(*words)
-    out = ctypes.c_void_p()
-    with torch.cuda.device(device):
-        call("sod_stream_create_cumask", ctypes.cast(arr, ctypes.c_void_p), len(words), ctypes.byref(out))
-    return torch.cuda.ExternalStream(out.value, device=device)       # lives for the rest of the process
-
-
-def register_compute_stream(device, stream):
-    """Announce an extra stream that runs backward nodes (e.g. the FCOS box tower's).  Parameter gradients may be produced on it, so
-    the bucket reducer (arena._launch_bucket) waits for it in addition to the launching node's stream and the wgrad side stream."""
-    lst = _aux_streams.setdefault(device.index, [])
-    if all(s.cuda_stream != stream.cuda_stream for s in lst):
-        lst.append(stream)
-
-
-def aux_compute_streams(device):
-    return list(_aux_streams.get(device.index, ()))
-
-
-# (Two or three round-robin side streams measured neutral to worse in rounds 2 and 4 - 614.7 / 606 vs 613.8 img/s, 640.3 vs 642.0 - and left
-# the tree in round 5: one in-order side stream.)
-
-
-def wgrad_side_streams(device):
-    """The side streams of ``device`` on which wgrad work may be pending in this backward pass (empty list if none)."""
-    return list(_side_streams.get(device.index, ())) if _side_join_queued else []
-
-
-# Re-pairing the backward phases by roof (round 6; SOD_HOLD_HEAD_WGRAD=0 restores the old order).  The head towers' weight gradients are
-# MFMA-bound, and so are the towers' data gradients they used to run beside (8.5 ms phase on three queues); the FPN / backbone backward
-# that follows is HBM-bound on two saturated queues.  The tower units therefore PARK their weight-gradient launches (and the mark_ready
-# behind them) and the first FPN / backbone backward node releases them, in order, onto the same side stream: they then run beside the
-# HBM-bound kernels.  Same launches, same operands, same results; measured on the FCOS R50 step in alternating 60-step runs:
-# 660.3 -> 665.3, 653.5 -> 661.7, 655.7 -> 660.8 img/s (+0.8 ... +1.2 %), one-rank RCCL rehearsal 646.5 -> 654.2 with the exposed
-# communication unchanged (0.13 ms per step: the head's bucket is launched later, but 7 ms of backward are still ahead of it).  Releasing
-# them onto a side stream of their OWN instead measured 14 % SLOWER (555 - 567 img/s at 4, 5 or 6 hardware queues): three streams of
-# chip-filling kernels take each other's CUs; profiles/r6_pairing.txt.
-HOLD_HEAD_WGRAD = os.environ.get("SOD_HOLD_HEAD_WGRAD", "1") != "0"
-_held = []
-
-
-def hold_or_call(fn):
-    """Tower units: run ``fn`` (weight-gradient launch + mark_ready) now, or park it until release_held()."""
-    if HOLD_HEAD_WGRAD and _side_join_queued_or_in_backward():
-        _held.append(fn)
-    else:
-        fn()
-
-
-def _side_join_queued_or_in_backward():
-    """Parking is only safe when something will release: inside an autograd backward pass (the end-of-backward callback does, at the
-    latest).  Op-level calls outside a backward pass launch at once."""
-    global _side_join_queued
-    if _side_join_queued:
-        return True
-    try:
-        torch.autograd.Variable._execution_engine.queue_callback(_wgrad_join)
-    except RuntimeError:
-        return False
-    _side_join_queued = True
-    return True
-
-
-def release_held():
-    """First FPN / backbone backward node (and the end-of-backward join, at the latest): issue every parked launch, in order."""
-    if _held:
-        items = list(_held)
-        _held.clear()
-        for fn in items:
-            fn()
-
-
-def drop_held():
-    """A backward pass that ended in an exception may leave parked launches behind: never carry them into the next step."""
-    _held.clear()
-
-
-def _wgrad_join():
-    global _side_join_queued
-    release_held()
-    _side_join_queued = False
-    for idx, sides in _side_streams.items():
-        main = torch.cuda.current_stream(idx)
-        for side in sides:
-            main.wait_stream(side)
-    _side_keep.clear()      # the main stream now waits for every side-stream reader: the operands may go back to its pool
-
-
-def wgrad_join():
-    """Make the current stream(s) wait for every weight-gradient launch enqueued so far.  The end-of-backward callback does this
-    on the normal path; the optimizer and the bucket reducer call it again so that a backward pass that ended in an exception (the
-    callback never ran) cannot leave gradients in flight.  A no-op when no side stream exists."""
-    if _side_streams:
-        _wgrad_join()
-
-
-# ---- batched hand-over to the side stream.  Every hand-over costs an event RECORD on the producing stream and a WAIT on the side stream;
-# the kernel trace prices each at 6-7 us of queue bubble (the next kernel of that queue starts that much later: 70 hand-overs per FCOS
-# step = 0.45 ms on the main queue and as much on the side queue, profiles/r5_step_occupancy.txt).  Inside ``with wgrad_batch():`` the
-# weight- / bias-gradient launches (and the arena.mark_ready calls that follow them) are collected and issued together when the block ends:
-# ONE record + ONE wait for all of them.  A residual block's three or four weight gradients then cost one hand-over instead of four.
-import threading as _threading
-
-_batch_tls = _threading.local()
-
-
-class wgrad_batch:
-    def __enter__(self):
-        self.outer = getattr(_batch_tls, "items", None)
-        if self.outer is None:
-            _batch_tls.items = []
-        return self
-
-    def __exit__(self, et, ev, tb):
-        if self.outer is None:
-            items, _batch_tls.items = _batch_tls.items, None
-            if et is None and items:
-                _batch_tls.flushing, _batch_tls.waited = True, set()
-                try:
-                    for fn in items:
-                        fn()
-                finally:
-                    _batch_tls.flushing, _batch_tls.waited = False, None
-        return False
-
-
-def _batch_defer(fn):
-    """True if ``fn`` was queued into the open batch of this thread (the caller returns without launching)."""
-    items = getattr(_batch_tls, "items", None)
-    if items is None or not WGRAD_BATCH:
-        return False
-    items.append(fn)
-    return True
-
-
-def batch_or_call(fn):
-    """Run ``fn`` now, or behind the launches already collected in the open batch (arena.mark_ready: a bucket must not be handed to the
-    reducer before the launches that fill it have been issued)."""
-    if not _batch_defer(fn):
-        fn()
-
-
-# False: one hand-over per weight-gradient launch (as until round 4).  Batching a whole residual block's weight gradients behind its data
-# gradients measured SLOWER (623 vs 634 img/s, four alternating 100-step pairs, round 5: the side stream is the one that finishes last, and
-# launches that reach it later lengthen the tail of backward by more than the bubbles save), so only launches that were adjacent anyway
-# (weight + bias gradient of one convolution, conv1 + shortcut of a block) share a hand-over.
-WGRAD_BATCH = True
-
-
-def _wgrad_stream(device, tensors, key=None):
-    """Returns the stream to launch a wgrad on (None = current stream).  ``key`` identifies the gradient buffer: launches that add to
-    the same buffer always use the same stream (the slab / deterministic reductions update it with plain read-modify-writes)."""
-    global _side_join_queued
-    if not WGRAD_SIDE_STREAM or device.type != "cuda":
-        return None
-    if not _side_join_queued:
-        try:
-            torch.autograd.Variable._execution_engine.queue_callback(_wgrad_join)
-        except RuntimeError:     # not inside a backward pass (op-level calls): nobody would join, stay on the current stream
-            return None
-        _side_join_queued = True
-    sides = _side_streams.get(device.index)
-    if sides is None:
-        # lowest HIP stream priority (range on MI355X: 1 .. -1): the data-gradient chain is the critical path.  Measured 491.5-492.3
-        # (low) / 491.8 (normal) / 483-484 (high) img/s
-        sides = _side_streams[device.index] = [make_stream(device, 1, "WGRAD")]
-    side = sides[0]
-    # one wait per batch flush (the closures of a batch run back to back on this thread: nothing was enqueued on the current stream in
-    # between, so the first launch's wait covers the others) - or one per launch outside a batch
-    cur = torch.cuda.current_stream(device)
-    if getattr(_batch_tls, "flushing", False):
-        tag = (side.cuda_stream, cur.cuda_stream)
-        if tag not in _batch_tls.waited:
-            side.wait_stream(cur)
-            _batch_tls.waited.add(tag)
-    else:
-        side.wait_stream(cur)
-    # The operands (dY, X) must outlive the side-stream kernel.  They are kept referenced until the join instead of
-    # Tensor.record_stream(): with record_stream the allocator cannot reuse a block until a GPU-side event has completed, and since the
-    # host runs several steps ahead of the GPU the pool grew from 10 GB to 52 GB; held references are released in main-stream order
-    # right after the join is enqueued, so the pool stays at its single-stream size plus one backward pass of gradients.
-    _side_keep.extend(t for t in tensors if t is not None)
-    return side
 CONV_RELU = 1
 CONV_RES_UP2 = 2
 
@@ -443,23 +241,22 @@ def wgrad_workspace(device, stream=None):
 
 
 def conv2d_wgrad(dy, x, dw, R, S, stride=1, pad=0, dil=1, dy_img_stride=0, x_img_stride=0, K=None, x_shape=None, splits=0, qscale=None,
-                 k_real=None, c_real=None):
-    """Accumulates into dw (K,R,S,C) fp32."""
+                 k_real=None, c_real=None, side=True):
+    """Accumulates into dw (K,R,S,C) fp32.  ``side=False``: on the current stream also inside a backward pass."""
     _chk(dy, torch.bfloat16, "dy"); _chk(x, torch.bfloat16, "x"); _chk(dw, torch.float32, "dw")
-    if _batch_defer(lambda: conv2d_wgrad(dy, x, dw, R, S, stride, pad, dil, dy_img_stride, x_img_stride, K, x_shape, splits, qscale, k_real, c_real)):
-        return dw
     N, H, W, C = x_shape if x_shape is not None else x.shape
     if K is None:
         K = dy.shape[-1]
-    side = _wgrad_stream(dw.device, (dy, x, qscale), dw.data_ptr())      # qscale is read by the kernel's last stage: keep it alive too
-    ws = wgrad_workspace(dw.device, side)
     diag = dw.shape[-1] != C and is_channel_window(C, K, dw.shape[-1])      # grouped convolution: dw is (K, R, S, 128), diagonal tiles only
-    e0 = _prof_begin(side, "conv_wgrad")
-    call("sod_conv2d_wgrad", ptr(dy), ptr(x), ptr(dw), ptr(qscale), N, H, W, C, K, R, S, stride, pad, dil, dy_img_stride, x_img_stride,
-         splits, (WGRAD_DETERMINISTIC if DETERMINISTIC else 0) | (WGRAD_DIAG if diag else 0), ptr(ws), ws.numel(), stream_ptr(side))
-    Ho, Wo = conv_out_size(H, W, R, S, stride, pad, dil)
-    _prof_end("conv_wgrad", 2.0 * N * Ho * Wo * (k_real or K) * R * S * (c_real or (CWIN if diag else C)), e0, (N, H, W, C, K, R, stride), side)
-    return dw
+
+    def launch(stream):
+        ws = wgrad_workspace(dw.device, stream)
+        e0 = _prof_begin(stream, "conv_wgrad")
+        call("sod_conv2d_wgrad", ptr(dy), ptr(x), ptr(dw), ptr(qscale), N, H, W, C, K, R, S, stride, pad, dil, dy_img_stride, x_img_stride,
+             splits, (WGRAD_DETERMINISTIC if DETERMINISTIC else 0) | (WGRAD_DIAG if diag else 0), ptr(ws), ws.numel(), stream_ptr(stream))
+        Ho, Wo = conv_out_size(H, W, R, S, stride, pad, dil)
+        _prof_end("conv_wgrad", 2.0 * N * Ho * Wo * (k_real or K) * R * S * (c_real or (CWIN if diag else C)), e0, (N, H, W, C, K, R, stride), stream)
+    return _side_launch(dw, (dy, x, qscale), launch, side)      # qscale is read by the kernel's last stage: keep it alive too
 
 
 def _ptr_arr(ts):
@@ -565,20 +362,19 @@ def conv2d_dgrad_ml(dys, wt, x_hws, stride=1, pad=0, dil=1, dy_img_stride=0, N=N
 def conv2d_wgrad_ml(dys, xs, dw, R, S, stride=1, pad=0, dil=1, dy_img_stride=0, K=None, splits=0, qscale=None, k_real=None):
     """Accumulates the weight gradient over all levels in one launch."""
     _chk(dw, torch.float32, "dw")
-    if _batch_defer(lambda: conv2d_wgrad_ml(dys, xs, dw, R, S, stride, pad, dil, dy_img_stride, K, splits, qscale, k_real)):
-        return dw
     N, C = xs[0].shape[0], xs[0].shape[3]
     if K is None:
         K = dys[0].shape[-1]
     hs, ws_ = [x.shape[1] for x in xs], [x.shape[2] for x in xs]
-    side = _wgrad_stream(dw.device, list(dys) + list(xs) + [qscale], dw.data_ptr())
-    ws = wgrad_workspace(dw.device, side)
-    e0 = _prof_begin(side, "conv_wgrad")
-    call("sod_conv2d_wgrad_ml", len(xs), _ptr_arr(dys), _ptr_arr(xs), ptr(dw), ptr(qscale), N, _int_arr(hs), _int_arr(ws_), C, K, R, S,
-         stride, pad, dil, dy_img_stride, splits, WGRAD_DETERMINISTIC if DETERMINISTIC else 0, ptr(ws), ws.numel(), stream_ptr(side))
-    fl = sum(2.0 * N * ho * wo * (k_real or K) * R * S * C for ho, wo in (conv_out_size(h, w, R, S, stride, pad, dil) for h, w in zip(hs, ws_)))
-    _prof_end("conv_wgrad", fl, e0, ("ml", N, tuple(hs), C, K, R, stride, tuple(ws_)), side)
-    return dw
+
+    def launch(stream):
+        ws = wgrad_workspace(dw.device, stream)
+        e0 = _prof_begin(stream, "conv_wgrad")
+        call("sod_conv2d_wgrad_ml", len(xs), _ptr_arr(dys), _ptr_arr(xs), ptr(dw), ptr(qscale), N, _int_arr(hs), _int_arr(ws_), C, K, R, S,
+             stride, pad, dil, dy_img_stride, splits, WGRAD_DETERMINISTIC if DETERMINISTIC else 0, ptr(ws), ws.numel(), stream_ptr(stream))
+        fl = sum(2.0 * N * ho * wo * (k_real or K) * R * S * C for ho, wo in (conv_out_size(h, w, R, S, stride, pad, dil) for h, w in zip(hs, ws_)))
+        _prof_end("conv_wgrad", fl, e0, ("ml", N, tuple(hs), C, K, R, stride, tuple(ws_)), stream)
+    return _side_launch(dw, list(dys) + list(xs) + [qscale], launch)
 
 
 def weight_prep(w_master, scale=None, want_krsc=True, want_crsk=True, cpad=None):
@@ -683,15 +479,14 @@ def bias_grad(dy, dbias, N, HW, C, img_stride=0, scale_num=None, scale_den=None,
     """dbias += [scale_num / max(scale_den * den_mul, den_min), device scalars] * per-channel sum of dy."""
     _chk(dy, torch.bfloat16, "dy"); _chk(dbias, torch.float32, "dbias")
     _chk(scale_num, torch.float32, "scale_num"); _chk(scale_den, torch.float32, "scale_den")
-    if _batch_defer(lambda: bias_grad(dy, dbias, N, HW, C, img_stride, scale_num, scale_den, den_mul, den_min)):
-        return dbias
-    side = _wgrad_stream(dbias.device, (dy, scale_num, scale_den), dbias.data_ptr())      # like the weight gradient: only the optimizer / all-reduce consumes it
-    if scale_num is None and scale_den is None:
-        call("sod_bias_grad", ptr(dy), ptr(dbias), N, HW, C, img_stride, *_det_ws(dbias.device, side), stream_ptr(side))
-    else:
-        call("sod_bias_grad_scaled", ptr(dy), ptr(dbias), ptr(scale_num), ptr(scale_den), float(den_mul), float(den_min), N, HW, C, img_stride,
-             *_det_ws(dbias.device, side), stream_ptr(side))
-    return dbias
+
+    def launch(stream):
+        if scale_num is None and scale_den is None:
+            call("sod_bias_grad", ptr(dy), ptr(dbias), N, HW, C, img_stride, *_det_ws(dbias.device, stream), stream_ptr(stream))
+        else:
+            call("sod_bias_grad_scaled", ptr(dy), ptr(dbias), ptr(scale_num), ptr(scale_den), float(den_mul), float(den_min), N, HW, C, img_stride,
+                 *_det_ws(dbias.device, stream), stream_ptr(stream))
+    return _side_launch(dbias, (dy, scale_num, scale_den), launch)      # like the weight gradient: only the optimizer / all-reduce consumes it
 
 
 def bias_grad_ml(dys, dbias):
@@ -701,16 +496,13 @@ def bias_grad_ml(dys, dbias):
     for t in dys:
         _chk(t, torch.bfloat16, "dy")
     N, C = dys[0].shape[0], dys[0].shape[-1]
-    if _batch_defer(lambda: bias_grad_ml(dys, dbias)):
-        return dbias
     if DETERMINISTIC or len(dys) > 6:
         for g in dys:
             bias_grad(g, dbias, N, g.numel() // (N * C), C)
         return dbias
-    side = _wgrad_stream(dbias.device, list(dys), dbias.data_ptr())
     hw = [g.numel() // (N * C) for g in dys]
-    call("sod_bias_grad_ml", len(dys), _ptr_arr(dys), ptr(dbias), N, ctypes.cast(_int_arr(hw), ctypes.c_void_p), C, stream_ptr(side))
-    return dbias
+    return _side_launch(dbias, list(dys), lambda stream: call("sod_bias_grad_ml", len(dys), _ptr_arr(dys), ptr(dbias), N,
+                                                              ctypes.cast(_int_arr(hw), ctypes.c_void_p), C, stream_ptr(stream)))
 
 
 def maxpool3x3s2(x):
@@ -1289,20 +1081,21 @@ def deform_conv_fwd_f32(x, offset, mask, w, bias, ksize, stride, pad, dil, dg=1,
     return y
 
 
-def deform_conv_wgrad_fused(dy, x, offset, mask, dw, ksize, stride, pad, dil, dg=1, off_ld=0, mask_ld=0, mask_is_logit=False, qscale=None):
-    """Accumulates the DeformConv weight gradient into dw (K, KH*KW*C elements, fp32) without a column buffer."""
-    _chk(dy, torch.bfloat16, "dy"); _chk(x, torch.bfloat16, "x"); _chk(dw, torch.float32, "dw")
+def deform_conv_wgrad_fused(dy, x, offset, mask, dw, ksize, stride, pad, dil, dg=1, off_ld=0, mask_ld=0, mask_is_logit=False, qscale=None,
+                            side=True):
+    """Accumulates the DeformConv weight gradient into dw (K, KH*KW*C elements, fp32) without a column buffer.  ``side``: as conv2d_wgrad."""
+    _chk(dy, torch.bfloat16, "dy"); _chk(x, torch.bfloat16, "x"); _chk(dw, torch.float32, "dw"); _chk(qscale, torch.float32, "qscale")
     N, H, W, C = x.shape
     KH, KW = ksize
     K = dy.shape[-1]
     if dw.numel() != K * KH * KW * C:
         raise _C.SlenderHipError("deform_conv_wgrad_fused: dw does not hold K x KH*KW*C elements")
-    side = _wgrad_stream(dw.device, (dy, x, offset, mask, qscale), dw.data_ptr())
-    ws = wgrad_workspace(dw.device, side)
-    _chk(qscale, torch.float32, "qscale")
-    call("sod_deform_conv_wgrad_fused", ptr(dy), ptr(x), ptr(offset), ptr(mask), ptr(dw), ptr(qscale), N, H, W, C, K, KH, KW, stride, pad, dil, dg, off_ld, mask_ld,
-         1 if mask_is_logit else 0, ptr(ws), ws.numel(), stream_ptr(side))
-    return dw
+
+    def launch(stream):
+        ws = wgrad_workspace(dw.device, stream)
+        call("sod_deform_conv_wgrad_fused", ptr(dy), ptr(x), ptr(offset), ptr(mask), ptr(dw), ptr(qscale), N, H, W, C, K, KH, KW, stride, pad, dil, dg, off_ld,
+             mask_ld, 1 if mask_is_logit else 0, ptr(ws), ws.numel(), stream_ptr(stream))
+    return _side_launch(dw, (dy, x, offset, mask, qscale), launch, side)
 
 
 def deform_fused_supported(C, K, dg):

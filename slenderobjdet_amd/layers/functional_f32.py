@@ -80,7 +80,7 @@ def conv2d_dgrad(dy, wt, x_hw, stride=1, pad=0, dil=1, accum=None, relu_mask=Non
 
 
 def conv2d_wgrad(dy, x, dw, R, S, stride=1, pad=0, dil=1, dy_img_stride=0, x_img_stride=0, K=None, x_shape=None, splits=0, qscale=None,
-                 k_real=None, c_real=None):
+                 k_real=None, c_real=None, side=True):      # (always the current stream here, whatever ``side`` says)
     _chk(dy, "dy"); _chk(x, "x"); _chk(dw, "dw"); _chk(qscale, "qscale")
     N, H, W, C = x_shape if x_shape is not None else x.shape
     if K is None:

@@ -13,6 +13,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from . import functional as HF
+from . import grad_sched as GS
 
 
 def _arena_of(mod):
@@ -291,17 +292,13 @@ class HipGroupedConv2d(HipConv2d):
     def wgrad_into(self, arena, g, x):
         """dW of the dense embedding into a scratch tensor on the CURRENT stream, diagonal blocks added to the arena gradient."""
         # as ONE unit behind whatever an open wgrad_batch has collected (the scratch tensor is consumed right after its launch)
-        HF.batch_or_call(lambda: self._wgrad_into_now(arena, g, x))
+        GS.batch_or_call(lambda: self._wgrad_into_now(arena, g, x))
 
     def _wgrad_into_now(self, arena, g, x):
         K, k, C = self.out_channels, self.kernel_size, self.in_channels
         win = self.windowed()
         dense = torch.zeros((K, k, k, HF.CWIN if win else C), dtype=torch.float32, device=g.device)
-        prev, HF.WGRAD_SIDE_STREAM = HF.WGRAD_SIDE_STREAM, False
-        try:
-            HF.conv2d_wgrad(g, x, dense, k, k, self.stride, self.padding, self.dilation, qscale=self.bn_scale)
-        finally:
-            HF.WGRAD_SIDE_STREAM = prev
+        HF.conv2d_wgrad(g, x, dense, k, k, self.stride, self.padding, self.dilation, qscale=self.bn_scale, side=False)
         arena.grad_view(self.weight).add_(self.window_blocks(dense) if win else self.blocks_of(dense))
         arena.mark_ready(self.weight)
 
@@ -336,9 +333,9 @@ class _ConvFn(torch.autograd.Function):
         g = HF.relu_bwd(dy, y) if (mod.relu and not mod.grad_premasked) else dy
         arena = _arena_of(mod)
         N, H, W, C = x.shape
-        HF.release_held()               # weight gradients the head towers parked (SOD_HOLD_HEAD_WGRAD=1; nothing otherwise)
+        GS.release_held()               # weight gradients the head towers parked (SOD_HOLD_HEAD_WGRAD=1; nothing otherwise)
         if mod.weight.requires_grad:
-            with HF.wgrad_batch():      # weight + bias gradient: one hand-over to the side stream
+            with GS.wgrad_batch():      # weight + bias gradient: one hand-over to the side stream
                 if getattr(mod, "groups", 1) > 1:
                     mod.wgrad_into(arena, g, x)
                 else:
@@ -387,8 +384,7 @@ class GradPark:
     def put(self, ptr, g):
         self.parked[ptr] = g
         if not self.hooked:
-            torch.autograd.Variable._execution_engine.queue_callback(self._check)
-            self.hooked = True
+            self.hooked = GS.at_end_of_backward(self._check)
 
     def _check(self):
         self.hooked = False
@@ -416,8 +412,7 @@ class SiblingFold:
         self.event = torch.cuda.Event()
         self.event.record(self.stream)
         if not self.hooked:
-            torch.autograd.Variable._execution_engine.queue_callback(self._check)
-            self.hooked = True
+            self.hooked = GS.at_end_of_backward(self._check)
 
     def take(self):
         part, self.partial = self.partial, None
@@ -499,7 +494,7 @@ class _ConvGnReluFn(torch.autograd.Function):
         def wgrad():
             HF.conv2d_wgrad_ml(dy1s, list(xs), arena.grad_view(conv.weight), k, k, conv.stride, conv.padding, conv.dilation)
             arena.mark_ready(conv.weight)
-        HF.hold_or_call(wgrad)          # (SOD_HOLD_HEAD_WGRAD=1: parked until the FPN backward starts; default: launched here)
+        GS.hold_or_call(wgrad)          # (SOD_HOLD_HEAD_WGRAD=1: parked until the FPN backward starts; default: launched here)
         dxs = [None] * nl
         if any(ctx.needs_input_grad[3:]):
             fold, ctx.fold = ctx.fold, None
@@ -580,12 +575,12 @@ class _ConvReluMLFn(torch.autograd.Function):
         else:
             gs = [HF.relu_bwd(dy.contiguous(), y) for dy, y in zip(dys, ys)]
         def wgrad():
-            with HF.wgrad_batch():
+            with GS.wgrad_batch():
                 HF.conv2d_wgrad_ml(gs, list(xs), arena.grad_view(conv.weight), 3, 3, 1, 1, 1)
                 arena.mark_ready(conv.weight)
                 HF.bias_grad_ml(gs, arena.grad_view(conv.bias))
                 arena.mark_ready(conv.bias)
-        HF.hold_or_call(wgrad)          # parked until the FPN backward starts (layers/functional.py: HOLD_HEAD_WGRAD)
+        GS.hold_or_call(wgrad)          # parked until the FPN backward starts (layers/grad_sched.py: HOLD_HEAD_WGRAD)
         dxs = [None] * nl
         if any(ctx.needs_input_grad[3:]):
             hw = [(x.shape[1], x.shape[2]) for x in xs]
@@ -636,7 +631,7 @@ class _ConvMLFn(torch.autograd.Function):
                 dy = HF.f32_to_bf16(dy)
             gs.append(HF.relu_bwd(dy, ys[i]) if unit.relu else dy)
         k = conv.kernel_size
-        with HF.wgrad_batch():
+        with GS.wgrad_batch():
             HF.conv2d_wgrad_ml(gs, list(xs), arena.grad_view(conv.weight), k, k, 1, conv.padding, 1)
             arena.mark_ready(conv.weight)
             HF.bias_grad_ml(gs, arena.grad_view(conv.bias))

@@ -11,6 +11,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from ...layers import functional as HF
+from ...layers import grad_sched as GS
 from ...layers.nn import DeferSlot, HipConv2d, HipGroupedConv2d, _arena_of, max_pool_3x3_s2
 import os
 
@@ -219,7 +220,7 @@ class _BottleneckStageFn(torch.autograd.Function):
             db = _dgrad(blk.conv3, g, b, relu_mask=b, reverse=True)
             _wgrad(blk.conv2, db, a, arena)
             da = _dgrad(blk.conv2, db, a, relu_mask=a)
-            with HF.wgrad_batch():       # adjacent launches: one hand-over to the side stream for both
+            with GS.wgrad_batch():       # adjacent launches: one hand-over to the side stream for both
                 _wgrad(blk.conv1, da, xin, arena)
                 if blk.shortcut is not None:
                     _wgrad(blk.shortcut, g, xin, arena)

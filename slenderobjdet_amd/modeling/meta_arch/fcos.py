@@ -25,6 +25,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from ...layers import functional as HF
+from ...layers import grad_sched as GS
 from ...layers.deform_conv import DFConv2d
 from ...layers.nn import ConvGnRelu, HipConv2d, HipGroupNorm, _arena_of, group_norm_relu
 from ...structures import Boxes, ImageList, Instances, PreparedInputs
@@ -150,8 +151,8 @@ class FCOSHead(nn.Module):
             # the box tower's stream at the HIGH HIP priority (-1): in backward it is the stream the main stream ends up waiting for (it
             # shares the CUs with the weight-gradient stream from its first kernel on).  Five + four alternating pairs of 100-step runs:
             # 642.9 vs 640.5 img/s (+0.4 %), every pair in favour; with the main stream high as well: 635.5 vs 641.2.
-            s2 = _tower_streams[dev.index] = HF.make_stream(dev, -1, "TOWER")
-            HF.register_compute_stream(dev, s2)
+            s2 = _tower_streams[dev.index] = GS.make_stream(dev, -1, "TOWER")
+            GS.register_compute_stream(dev, s2)
         s2.wait_stream(main)
         for f in feats:
             f.record_stream(s2)
@@ -258,7 +259,7 @@ class _FcosHeadLossFn(torch.autograd.Function):
             off += h * w
         grads = []
         preds = ((head.cls_pred, dcls, kcp, cls_t, head.kc), (head.box_pred, dbox, 8, box_t, 5 if head.centerness_on_reg else 4))
-        with HF.wgrad_batch():      # the four weight / bias gradient launches of the two prediction convs: one hand-over to the side stream
+        with GS.wgrad_batch():      # the four weight / bias gradient launches of the two prediction convs: one hand-over to the side stream
             for pred, dbuf, kk, tower, kr in preds:
                 dys = [dbuf.view(-1)[o * kk:] for o in offs]
                 HF.conv2d_wgrad_ml(dys, list(tower), arena.grad_view(pred.weight), 3, 3, 1, 1, 1, dy_img_stride=L * kk, K=kk, k_real=kr)
@@ -323,7 +324,7 @@ class FCOSV2(nn.Module):
             bottom.prepare_frozen_prefix()
         side = _prefetch_streams.get(dev.index)
         if side is None:
-            side = _prefetch_streams[dev.index] = HF.make_stream(dev, 0, "PREFETCH")
+            side = _prefetch_streams[dev.index] = GS.make_stream(dev, 0, "PREFETCH")
         side.wait_stream(main)
         self._prefetched = None
         with torch.cuda.stream(side):

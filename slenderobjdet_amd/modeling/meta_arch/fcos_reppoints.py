@@ -31,6 +31,7 @@ from torch import nn
 from torch.autograd.function import once_differentiable
 
 from ...layers import functional as HF
+from ...layers import grad_sched as GS
 from ...layers.deform_conv import DeformConv
 from ...layers.nn import ConvML, HipConv2d, _arena_of
 from ...utils import comm
@@ -252,7 +253,7 @@ class _FcosRpdLossFn(torch.autograd.Function):
             doi.append(d32)
         dl = [dlogits.view(-1)[o * kp:] for o in offs]
         dc = [dctr.view(-1)[o * 8:] for o in offs]
-        with HF.wgrad_batch():      # the weight / bias gradient launches of the three prediction convs: one hand-over to the side stream
+        with GS.wgrad_batch():      # the weight / bias gradient launches of the three prediction convs: one hand-over to the side stream
             HF.conv2d_wgrad_ml(dl, list(cf), arena.grad_view(head.logits.weight), 1, 1, 1, 0, 1, dy_img_stride=L * kp, K=kp, k_real=K)
             arena.mark_ready(head.logits.weight)
             HF.bias_grad(dlogits, arena.grad_view(head.logits.bias), N, L, kp)

@@ -14,7 +14,7 @@ import torch.nn as nn
 
 from .. import _C
 from .._C import call, ptr, stream_ptr
-from ..layers import functional as HF
+from ..layers import grad_sched as GS
 from ..layers.nn import HipGroupNorm
 
 _NORM_TYPES = (nn.BatchNorm1d, nn.BatchNorm2d, nn.BatchNorm3d, nn.SyncBatchNorm, nn.GroupNorm, nn.InstanceNorm1d,
@@ -102,7 +102,7 @@ class FusedSGD(torch.optim.Optimizer):
         g0 = self.param_groups[0]
         lr_now = self.param_groups[self._ref_group]["lr"] / self._ref_mult
         a = self.arena
-        HF.wgrad_join()
+        GS.join()
         call("sod_sgd_step", ptr(a.params), ptr(a.grads), ptr(a.momentum), ptr(self._segs), self._nseg, None, float(lr_now),
              float(g0["momentum"]), 1 if g0["nesterov"] else 0, 1 if self._steps == 0 else 0, float(self.grad_scale), stream_ptr())
         self._steps += 1
@@ -170,7 +170,7 @@ class FusedAdaptive(torch.optim.Optimizer):
         else:
             bc1, bc2s = 1.0 - b1 ** t, (1.0 - b2 ** t) ** 0.5
         a = self.arena
-        HF.wgrad_join()
+        GS.join()
         call("sod_adaptive_step", ptr(a.params), ptr(a.grads), ptr(self.exp_avg), ptr(self.exp_avg_sq), ptr(self._segs), self._nseg,
              self.MODES[self.kind], float(lr_now), float(b1), float(b2), float(g0["eps"]), float(bc1), float(bc2s), float(self.grad_scale), stream_ptr())
         a.bump()

@@ -434,12 +434,13 @@ def test_fcos_r50_full_size_step(cuda):
 
 
 def test_side_streams_gradients_match_single_stream(cuda):
-    """The weight gradients enqueued on the side stream (layers/functional.py:_wgrad_stream) and the box tower's nodes on the tower
-    stream (FCOSHead.run_towers) must be complete when backward() returns.  In deterministic mode no float atomics are left, so
-    every stream configuration must give the single-stream gradients bit for bit; a gradient still in flight (or lost, or read before
-    its producer finished) would show up as a difference."""
+    """The weight gradients enqueued on the scheduler's side stream (layers/grad_sched.py: side_stream) and the box tower's nodes on
+    the tower stream (FCOSHead.run_towers) must be complete when backward() returns.  In deterministic mode no float atomics are
+    left, so every stream configuration must give the single-stream gradients bit for bit; a gradient still in flight (or lost, or
+    read before its producer finished) would show up as a difference."""
     from slenderobjdet_amd.data import synthetic_batch
     from slenderobjdet_amd.layers import functional as HF
+    from slenderobjdet_amd.layers import grad_sched as GS
     from slenderobjdet_amd.modeling.meta_arch import fcos as fcos_mod
 
     cfg, model, opt = _build(18, seed=3)
@@ -456,8 +457,8 @@ def test_side_streams_gradients_match_single_stream(cuda):
             # no synchronize here: reading .grad on the current stream must already be ordered after the other streams
             g = model.arena.grads.clone()
             if side:
-                assert HF._side_streams, "side stream was not used"
-                assert not HF._side_join_queued, "end-of-backward join did not run"
+                assert GS.sched.sides, "side stream was not used"
+                assert not GS.sched.join_queued, "end-of-backward join did not run"
             if tower:
                 assert fcos_mod._tower_streams, "tower stream was not used"
             if (False, False) in saved:
@@ -468,6 +469,58 @@ def test_side_streams_gradients_match_single_stream(cuda):
         assert torch.isfinite(saved[(False, False)]).all() and float(saved[(False, False)].abs().sum()) > 0
     finally:
         HF.WGRAD_SIDE_STREAM, fcos_mod.TOWER_STREAMS, HF.DETERMINISTIC = prev
+
+
+def test_failed_backward_adds_nothing_to_the_next_step(cuda):
+    """A backward pass that raises (a host exception from a tensor hook on an FPN output: the head towers have parked their weight
+    gradients by then, and the end-of-backward callback never runs) must leave nothing behind: the next good step gives the gradients
+    of the same step on a freshly built model bit for bit (deterministic mode), after zero_grad and also after a bare wgrad_join(),
+    which adds nothing of the dead step to the arena."""
+    from slenderobjdet_amd.data import synthetic_batch
+    from slenderobjdet_amd.layers import functional as HF
+    from slenderobjdet_amd.layers import grad_sched as GS
+
+    data = synthetic_batch(2, 320, 384, 3, device="cuda")
+    prev = HF.DETERMINISTIC, HF.WGRAD_SIDE_STREAM, GS.HOLD_HEAD_WGRAD
+    HF.DETERMINISTIC, HF.WGRAD_SIDE_STREAM, GS.HOLD_HEAD_WGRAD = True, True, True
+
+    def step(model, opt, fail=False):
+        def boom(g):
+            raise RuntimeError("boom in the FPN hook")
+
+        def arm(mod, inp, out):
+            out[model.in_features[-1]].register_hook(boom)      # P7: the FPN node that runs first in backward, before any release
+
+        opt.zero_grad()
+        handle = model.backbone.register_forward_hook(arm) if fail else None
+        try:
+            total = sum(model(data).values())
+        finally:
+            if handle is not None:
+                handle.remove()
+        model.arena.begin_backward(); total.backward(); model.arena.finish_backward()
+        return model.arena.grads.clone()
+
+    try:
+        ref = step(*_build(18, seed=3)[1:])
+        assert torch.isfinite(ref).all() and float(ref.abs().sum()) > 0
+        _, model, opt = _build(18, seed=3)
+        with pytest.raises(RuntimeError, match="boom in the FPN hook"):
+            step(model, opt, fail=True)
+        assert GS.sched.held, "the towers parked nothing: the failing step does not exercise the path"
+        assert torch.equal(step(model, opt), ref)               # zero_grad, then a good step
+        assert not GS.sched.held and not GS.sched.join_queued
+        with pytest.raises(RuntimeError, match="boom in the FPN hook"):
+            step(model, opt, fail=True)
+        torch.cuda.synchronize()
+        snap = model.arena.grads.clone()                        # what the dead step did launch before it died
+        HF.wgrad_join()
+        torch.cuda.synchronize()
+        assert torch.equal(model.arena.grads, snap)             # its parked launches were dropped, not issued
+        assert not GS.sched.held and not GS.sched.join_queued and not GS.sched.keep
+        assert torch.equal(step(model, opt), ref)
+    finally:
+        HF.DETERMINISTIC, HF.WGRAD_SIDE_STREAM, GS.HOLD_HEAD_WGRAD = prev
 
 
 def test_sgd_kernel_matches_oracle(cuda):
