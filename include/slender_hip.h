@@ -942,8 +942,19 @@ int sod_proposal_ar(const int* gt_off, const float* gt_box, const int* gt_cls, c
  *   test is generic: gt g is ignored for range a when gt_crowd[g] or gt_val[g] < lo[a] or gt_val[g] > hi[a], an unmatched detection
  *   when dt_val[d] is outside [lo[a], hi[a]] (gt_val [G], dt_val [N] float64: areas for COCO's area ranges, side ratios for the
  *   slenderness ranges).  scratch_off [num_seg]: offset in floats (even) of the segment's slot in `scratch` (8-byte aligned), needed
- *   where sod_coco_match_rotated_scratch_floats(G, max_det) > 0. */
+ *   where sod_coco_match_rotated_scratch_floats(G, max_det) > 0.
+ * sod_proposal_ar_rotated: sod_proposal_ar - parameters, rounds, ties, outputs, the caller's zeroing - on rotated boxes: gt_box5 [G, 5] /
+ *   dt_box5 [N, 5] float32 (cx, cy, w, h, angle in degrees).  The overlap is pairwise_iou_rotated(dt, gt) in float32, the function
+ *   behind sod_box_iou_rotated and sod_coco_match_rotated (a gt or detection with a zero side overlaps nothing); a gt's area bucket is
+ *   decided by the float32 product w * h of its box, its ratio bucket by gt_ratio [G].  scratch_off [num_img] in floats where
+ *   sod_proposal_ar_rotated_scratch_floats(G, limit) > 0: 0 while G * limit <= 3200 (both matrices in LDS), else 2 * limit * G; -1 for
+ *   a negative argument. */
 long long sod_coco_match_rotated_scratch_floats(int num_gts, int max_det);
+long long sod_proposal_ar_rotated_scratch_floats(int num_gts, int limit);
+int sod_proposal_ar_rotated(const int* gt_off, const float* gt_box5, const int* gt_cls, const float* gt_ratio, const int* dt_off,
+                            const long long* dt_order, const float* dt_box5, const int* dt_cls, int num_img, int limit, int K1,
+                            const float* thr, int T, const float* ratio_rng, int R, const float* area_rng, int A,
+                            const long long* scratch_off, float* scratch, int* hits, int* counts, float* recalls, void* stream);
 int sod_coco_match_rotated(const int* gt_off, const float* gt_box5, const unsigned char* gt_crowd, const double* gt_val,
                            const int* dt_off, const float* dt_box5, const double* dt_val, int num_seg, int num_img, int max_det,
                            const double* iou_thr, int T, const double* ranges, int A, const long long* scratch_off, float* scratch,

@@ -195,6 +195,8 @@ _SIGS = {
     "sod_proposal_ar": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "sod_coco_match_rotated_scratch_floats": [_I, _I],
     "sod_coco_match_rotated": [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P],
+    "sod_proposal_ar_rotated_scratch_floats": [_I, _I],
+    "sod_proposal_ar_rotated": [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P, _I, _P, _I, _P, _I, _P, _P, _P, _P, _P, _P],
     "sod_retina_label_rotated": [_P, _I, _P, _P, _P, _I, _I, _F, _F, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P],
     "sod_retina_box5_loss_fwd": [_P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _F, _P, _P],
     "sod_retina_box5_loss_bwd": [_P, _I, _P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
@@ -217,7 +219,7 @@ _SIGS = {
 }
 _RESTYPES = {"sod_reduce_workspace_bytes": c_longlong, "sod_conv2d_wgrad_workspace_bytes": c_longlong, "sod_nms_workspace_bytes": c_longlong, "sod_batched_nms_workspace_bytes": c_longlong, "sod_version": c_char_p,
              "sod_coco_match_scratch_doubles": c_longlong, "sod_proposal_ar_scratch_floats": c_longlong,
-             "sod_coco_match_rotated_scratch_floats": c_longlong}
+             "sod_coco_match_rotated_scratch_floats": c_longlong, "sod_proposal_ar_rotated_scratch_floats": c_longlong}
 
 
 class SlenderHipError(RuntimeError):

@@ -1,6 +1,7 @@
 // COCO box evaluation for rotated boxes (cx, cy, w, h, angle_deg) on device: the per-(image, category) greedy matching of
 // detectron2's RotatedCOCOeval.computeIoU (pairwise_iou_rotated, float32) under pycocotools' COCOeval.evaluateImg
 // (call site train_net.py:60-62, evaluator type "rotated_coco").  The accumulation is sod_coco_accumulate (coco_eval.hip), unchanged.
+// The slenderness-bucketed recall pass (AR / mAR) on rotated boxes is the skeleton of proposal_ar.h under the box policy ArRotBox.
 //
 // The IoU is iou_rotated_impl of rotated_iou.h with the candidate points in LDS - the function box_iou_rotated and the rotated NMS
 // run, so a threshold decides here on the same float32 bits as there.
@@ -113,7 +114,34 @@ __global__ __launch_bounds__(64) void coco_match_rotated_kernel(const int* __res
   }
 }
 
+#include "proposal_ar.h"
+
+// The recall pass on rotated boxes.  Two of the four waves stage the matrices: 24 candidate points x 128 lanes x 8 B = 24 KB of LDS beside
+// the two staged matrices (25.6 KB) and the reduction arrays (6 KB) - 55.6 KB of the 64 KB a workgroup may declare; with all 256 lanes the
+// points alone would take 48 KB.  The rounds run on all four waves.  A gt's area bucket is decided by the float32 product w * h.
+struct ArRotBox {
+  static constexpr int W = 5;
+  static constexpr int STAGE_LANES = 128;
+  using Lds = P2;
+  static constexpr int LDS_PER_LANE = 24;
+  static __device__ __forceinline__ float overlap(const float* d, const float* g, Lds* lds) {
+    return iou_rotated_lds(d, g, lds, STAGE_LANES);
+  }
+  static __device__ __forceinline__ float area(const float* g) { return g[2] * g[3]; }
+};
+
 }  // namespace
+
+extern "C" long long sod_proposal_ar_rotated_scratch_floats(int num_gts, int limit) { return proposal_ar_scratch_floats(num_gts, limit); }
+
+extern "C" int sod_proposal_ar_rotated(const int* gt_off, const float* gt_box5, const int* gt_cls, const float* gt_ratio, const int* dt_off,
+                                       const long long* dt_order, const float* dt_box5, const int* dt_cls, int num_img, int limit, int K1,
+                                       const float* thr, int T, const float* ratio_rng, int R, const float* area_rng, int A,
+                                       const long long* scratch_off, float* scratch, int* hits, int* counts, float* recalls,
+                                       void* stream) {
+  return launch_proposal_ar<ArRotBox>(gt_off, gt_box5, gt_cls, gt_ratio, dt_off, dt_order, dt_box5, dt_cls, num_img, limit, K1, thr, T,
+                                      ratio_rng, R, area_rng, A, scratch_off, scratch, hits, counts, recalls, stream);
+}
 
 extern "C" long long sod_coco_match_rotated_scratch_floats(int num_gts, int max_det) {
   if (num_gts < 0 || max_det < 0) return -1;

@@ -109,6 +109,7 @@ class CocoGt:
             self.ratios = oriented_ratios(self.anns, ratio_device)
         self._arrays = None
         self._rotated_arrays = None
+        self._rotated_recall_arrays = None
 
     def _segment_order(self):
         """(image index of every annotation or -1, the annotations of known images and categories ordered by (category, image)
@@ -158,8 +159,16 @@ class CocoGt:
         ValueError for a dataset that holds both a five-number box and a crowd gt: the rotated IoU has no crowd form."""
         if self._rotated_arrays is not None:
             return self._rotated_arrays
-        n = len(self.anns)
         _, order, seg_gt_off = self._segment_order()
+        box5, area, ratio, crowd = self._rotated_boxes()
+        self._rotated_arrays = dict(seg_gt_off=seg_gt_off, seg_box5=np.ascontiguousarray(box5[order]), seg_crowd=crowd[order],
+                                    seg_area=area[order], seg_ratio5=ratio[order])
+        return self._rotated_arrays
+
+    def _rotated_boxes(self):
+        """Per annotation in json order: box5 [n, 5] f32, area [n] f64, ratio [n] f64, crowd [n] u8 (``iscrowd`` or ``ignore``) by the
+        rules of rotated_arrays(), whose errors it raises."""
+        n = len(self.anns)
         five = [len(a["bbox"]) == 5 for a in self.anns]
         if any(len(a["bbox"]) not in (4, 5) for a in self.anns):
             raise ValueError("a bbox must hold 4 (XYWH) or 5 (cx, cy, w, h, angle) numbers")
@@ -178,6 +187,24 @@ class CocoGt:
             area[j] = float(a["area"]) if "area" in a else w * h
             ratio[j] = float(a["ratio"]) if "ratio" in a else (min(w, h) / max(w, h) if max(w, h) > 0 else 0.0)
         crowd = np.array([1 if (a.get("iscrowd", 0) or a.get("ignore", 0)) else 0 for a in self.anns], np.uint8)
-        self._rotated_arrays = dict(seg_gt_off=seg_gt_off, seg_box5=np.ascontiguousarray(box5[order]), seg_crowd=crowd[order],
-                                    seg_area=area[order], seg_ratio5=ratio[order])
-        return self._rotated_arrays
+        return box5, area, ratio, crowd
+
+    def rotated_recall_arrays(self):
+        """The gt side of the rotated recall pass (cached): the non-crowd gts (neither ``iscrowd`` nor ``ignore``) of the known images,
+        ordered by image and in json order within one -
+        img_gt_off [I+1] i32 / img_box5 [G', 5] f32 / img_cls [G'] i32 contiguous ids through the metadata map / img_ratio5 [G'] f32.
+        Boxes and ratios by the rules of rotated_arrays(), whose errors it raises."""
+        if self._rotated_recall_arrays is not None:
+            return self._rotated_recall_arrays
+        I = len(self.img_ids)
+        img_idx = {im: i for i, im in enumerate(self.img_ids)}
+        img_of = np.array([img_idx.get(a["image_id"], -1) for a in self.anns], np.int64)
+        box5, _, ratio, crowd = self._rotated_boxes()
+        keep = np.nonzero((img_of >= 0) & (crowd == 0))[0]
+        keep = keep[np.argsort(img_of[keep], kind="stable")]
+        img_gt_off = np.zeros(I + 1, np.int32)
+        np.cumsum(np.bincount(img_of[keep], minlength=I), out=img_gt_off[1:])
+        img_cls = np.array([self.id_map[self.anns[j]["category_id"]] for j in keep], np.int32)
+        self._rotated_recall_arrays = dict(img_gt_off=img_gt_off, img_box5=np.ascontiguousarray(box5[keep]), img_cls=img_cls,
+                                           img_ratio5=ratio[keep].astype(np.float32))
+        return self._rotated_recall_arrays

@@ -5,7 +5,8 @@
     ar          sod_proposal_ar      _evaluate_predictions_ar, one workgroup per image
 
 run_rotated is the rotated-box evaluation (detectron2's RotatedCOCOeval): sod_coco_match_rotated (csrc/coco_eval_rotated.hip) on
-(cx, cy, w, h, angle) boxes with COCO's area ranges or the slenderness ranges, then the same sod_coco_accumulate.
+(cx, cy, w, h, angle) boxes with COCO's area ranges or the slenderness ranges, then the same sod_coco_accumulate.  run_rotated_ar is the
+"ar" pass on those boxes (sod_proposal_ar_rotated): the rounds of sod_proposal_ar with the rotated IoU as the overlap.
 
 Ordering uses stable device sorts on packed int64 keys (segment or category in the high word, -score mapped to an order-preserving
 unsigned word in the low one): one sort puts every segment's detections in stable descending score order, a second gives each
@@ -106,6 +107,22 @@ class RotatedGtDevice(GtDevice):
             t(h[k]) for k in ("seg_gt_off", "seg_box5", "seg_crowd", "seg_area", "seg_ratio5"))
         off, n = _scratch_offsets(np.diff(h["seg_gt_off"]), lambda g: lib.sod_coco_match_rotated_scratch_floats(g, MAX_DETS[-1]))
         self.match_scratch_off, self.match_scratch = t(off), torch.empty(max(n, 2), dtype=torch.float32, device=device)
+        self._gt, self._device, self._recall = gt, device, None
+
+    def recall(self):
+        """The gt arrays of CocoGt.rotated_recall_arrays() on the device with the scratch layout of the rotated recall pass: built at the
+        first call, so an evaluation without that pass neither uploads nor allocates them."""
+        if self._recall is None:
+            lib = _C.load()
+            h = self._gt.rotated_recall_arrays()
+            if len(h["img_cls"]) and not (0 <= h["img_cls"].min() and h["img_cls"].max() < self.K):
+                raise ValueError("thing_dataset_id_to_contiguous_id must map the categories onto 0 .. K-1")
+            t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self._device)  # noqa: E731
+            r = {k: t(h[k]) for k in ("img_gt_off", "img_box5", "img_cls", "img_ratio5")}
+            off, n = _scratch_offsets(np.diff(h["img_gt_off"]), lambda g: lib.sod_proposal_ar_rotated_scratch_floats(g, AR_LIMIT))
+            r["scratch_off"], r["scratch"] = t(off), torch.empty(max(n, 1), dtype=torch.float32, device=self._device)
+            self._recall = r
+        return self._recall
 
 
 def _ev(events, name):
@@ -158,6 +175,30 @@ def _accumulate(gd, seg_s, score_s, rank, matched, ignored, npig, A, st):
     return precision, recall, sc
 
 
+def _recall_pass(sym, gt, scratch_off, scratch, ii, cl, boxes, I, K, st):
+    """The recall pass ``sym`` (sod_proposal_ar / sod_proposal_ar_rotated) over the predictions in prediction order: gt = (img_gt_off,
+    boxes, classes, ratios) by image, ii / cl the image index and contiguous class of every prediction, boxes [N, 4 or 5] float32.
+    Returns recalls [T, K+1, R, A] float32, counts [K+1, R, A] int32, hits [T, K+1, R, A] int32."""
+    dev = boxes.device
+    K1 = K + 1                                                     # the reference's len(cats) + 1, "all classes" last
+    Ra, Aa = len(AR_RATIOS), len(AR_AREAS)
+    perm3 = torch.sort(ii, stable=True).indices
+    img_off = torch.searchsorted(ii[perm3], torch.arange(I + 1, device=dev)).int()
+    thr = ar_thresholds().numpy()
+    Ta = len(thr)
+    rr = np.array(list(AR_RATIOS.values()), np.float32).reshape(-1)
+    aa = np.array(list(AR_AREAS.values()), np.float32).reshape(-1)
+    hits = torch.zeros((Ta, K1, Ra, Aa), dtype=torch.int32, device=dev)
+    counts = torch.zeros((K1, Ra, Aa), dtype=torch.int32, device=dev)
+    recalls = torch.empty((Ta, K1, Ra, Aa), dtype=torch.float32, device=dev)
+    dt_cls = cl.int().contiguous()
+    gt_off, gt_box, gt_cls, gt_ratio = gt
+    _C.call(sym, _C.ptr(gt_off), _C.ptr(gt_box), _C.ptr(gt_cls), _C.ptr(gt_ratio), _C.ptr(img_off), _C.ptr(perm3), _C.ptr(boxes),
+            _C.ptr(dt_cls), I, AR_LIMIT, K1, _hp(thr), Ta, _hp(rr), Ra, _hp(aa), Aa, _C.ptr(scratch_off), _C.ptr(scratch), _C.ptr(hits),
+            _C.ptr(counts), _C.ptr(recalls), st)
+    return recalls, counts, hits
+
+
 def run(gd, image_id, boxes_xyxy, scores, classes, check=True, events=None):
     """image_id [N] int64, boxes_xyxy [N, 4] float32, scores [N] float32, classes [N] int64 contiguous ids - device tensors in
     prediction order.  Returns device tensors: precision / scores [T, R, K, A, M], recall [T, K, A, M] float64, recalls
@@ -185,21 +226,8 @@ def run(gd, image_id, boxes_xyxy, scores, classes, check=True, events=None):
     _ev(events, "accumulate")
     precision, recall, sc = _accumulate(gd, seg_s, score_s, rank, matched, ignored, npig, A, st)
     _ev(events, "ar")
-    K1 = K + 1                                                     # the reference's len(cats) + 1, "all classes" last
-    Ra, Aa = len(AR_RATIOS), len(AR_AREAS)
-    perm3 = torch.sort(ii, stable=True).indices
-    img_off = torch.searchsorted(ii[perm3], torch.arange(I + 1, device=dev)).int()
-    thr = ar_thresholds().numpy()
-    Ta = len(thr)
-    rr = np.array(list(AR_RATIOS.values()), np.float32).reshape(-1)
-    aa = np.array(list(AR_AREAS.values()), np.float32).reshape(-1)
-    hits = torch.zeros((Ta, K1, Ra, Aa), dtype=torch.int32, device=dev)
-    counts = torch.zeros((K1, Ra, Aa), dtype=torch.int32, device=dev)
-    recalls = torch.empty((Ta, K1, Ra, Aa), dtype=torch.float32, device=dev)
-    dt_cls = cl.int().contiguous()
-    _C.call("sod_proposal_ar", _C.ptr(gd.img_gt_off), _C.ptr(gd.img_box), _C.ptr(gd.img_cls), _C.ptr(gd.img_ratio), _C.ptr(img_off),
-            _C.ptr(perm3), _C.ptr(xywh), _C.ptr(dt_cls), I, AR_LIMIT, K1, _hp(thr), Ta, _hp(rr), Ra, _hp(aa), Aa,
-            _C.ptr(gd.ar_scratch_off), _C.ptr(gd.ar_scratch), _C.ptr(hits), _C.ptr(counts), _C.ptr(recalls), st)
+    recalls, counts, hits = _recall_pass("sod_proposal_ar", (gd.img_gt_off, gd.img_box, gd.img_cls, gd.img_ratio), gd.ar_scratch_off,
+                                         gd.ar_scratch, ii, cl, xywh, I, K, st)
     _ev(events, "end")
     return {"precision": precision, "recall": recall, "scores": sc, "recalls": recalls, "counts": counts, "hits": hits,
             "dt_matched": matched, "dt_ignored": ignored, "npig": npig, "perm1": perm1, "rank": rank}
@@ -242,3 +270,20 @@ def run_rotated(gd, image_id, boxes5, scores, classes, bucket="area", check=True
     _ev(events, "end")
     return {"precision": precision, "recall": recall, "scores": sc, "dt_matched": matched, "dt_ignored": ignored, "npig": npig,
             "perm1": perm1, "rank": rank, "dt_off": dt_off}
+
+
+def run_rotated_ar(gd, image_id, boxes5, scores, classes, check=True, events=None):
+    """The slenderness-bucketed recall pass (AR / mAR) on rotated boxes: sod_proposal_ar_rotated with the thresholds, the six ratio and
+    four area ranges and the 100-detection limit of the axis-aligned pass.  gd a RotatedGtDevice; the arguments as run_rotated (the pass
+    has no score order: ``scores`` only fixes the signature).  Returns device tensors recalls [T, K+1, R, A] float32, counts
+    [K+1, R, A] int32, hits [T, K+1, R, A] int32."""
+    st = _C.stream_ptr()
+    N = int(scores.shape[0])
+    b = boxes5.float().reshape(-1, 5).contiguous()
+    r = gd.recall()
+    ii, cl, _ = _locate(gd, image_id, classes, check and N)
+    _ev(events, "ar")
+    recalls, counts, hits = _recall_pass("sod_proposal_ar_rotated", (r["img_gt_off"], r["img_box5"], r["img_cls"], r["img_ratio5"]),
+                                         r["scratch_off"], r["scratch"], ii, cl, b, gd.I, gd.K, st)
+    _ev(events, "ar_end")
+    return {"recalls": recalls, "counts": counts, "hits": hits}

@@ -12,6 +12,12 @@ without ``area`` takes w * h (pycocotools raises); a prediction tensor with four
 ``ratio_buckets=True`` is an extension, not reference behaviour: the match pass runs a second time with the six slenderness
 ranges of the axis-aligned evaluator (a gt by ``ratio`` or min(w, h) / max(w, h) of its box, a detection by w / h) and
 ``results["bbox-ratios"]`` holds the 16 ratio-bucketed AP / AR numbers.
+
+``MetadataCatalog.get(name).rotated_recall = True`` adds the slenderness-bucketed recall pass of the axis-aligned evaluator on
+rotated boxes (sod_proposal_ar_rotated): ``results["ar"]`` with the keys of COCOEvaluator's - AR / mAR per area range and per ratio
+range at 100 detections - follows the keys above and ``self.recalls`` holds the [T, K+1, R, A] recalls.  A gt's area bucket is
+decided by w * h of its box, its ratio bucket by ``ratio`` or min(w, h) / max(w, h).  The switch travels in the metadata, as
+``ratio_device`` does: the constructor keeps its parameters.
 """
 import json
 import os
@@ -21,7 +27,7 @@ import torch
 
 from . import device as D
 from .coco_evaluation import COCOEvaluator
-from .results import derive_ratio_results, derive_rotated_results, summarize, summarize_area
+from .results import ar_results, derive_ratio_results, derive_rotated_results, summarize, summarize_area
 
 
 def boxes_to_rotated(boxes):
@@ -45,6 +51,8 @@ class RotatedCOCOEvaluator(COCOEvaluator):
         self._ratio_buckets = bool(ratio_buckets)
         self._gt.rotated_arrays()
         self.ratio_stats = self.ratio_precision = self.ratio_recall = None
+        self._rotated_recall = bool(self._metadata.get("rotated_recall", False))
+        self.recalls = None
 
     def _flat(self):
         if not self._chunks:
@@ -77,6 +85,10 @@ class RotatedCOCOEvaluator(COCOEvaluator):
             self.ratio_recall = out["recall"].cpu().numpy()
             self.ratio_stats = None if empty else summarize(self.ratio_precision, self.ratio_recall)
             results["bbox-ratios"] = derive_ratio_results(self.ratio_stats)
+        if self._rotated_recall:
+            out = D.run_rotated_ar(self._gt_dev, flat["image_id"], boxes, flat["scores"], flat["classes"], check=False, events=events)
+            self.recalls = out["recalls"].cpu()
+            results["ar"] = ar_results(self.recalls, out["counts"].cpu().to(torch.int64))
         return results
 
     def _write_results_json(self, flat):

@@ -6,11 +6,12 @@ match kernel) / accumulate (ordering + the accumulate kernel) / ar (ordering + t
 after a warm-up; the kernel launches of one evaluation (torch profiler); the wall time of the whole evaluate including the host
 summaries; and a hash of the output arrays.
 
-    python tools/bench_coco_eval.py [--images 5000] [--cats 80] [--dets 100] [--iters 5] [--seed 0] [--rotated]
+    python tools/bench_coco_eval.py [--images 5000] [--cats 80] [--dets 100] [--iters 5] [--seed 0] [--rotated [--recall]]
 
 ``--rotated`` times RotatedCOCOEvaluator.evaluate_flat on ``synthetic_rotated_coco`` at the same size (match / accumulate phases;
-there is no recall pass) and reports the share of the (detection, gt) pairs of the segments whose circumscribed circles meet, i.e.
-that go on towards the polygon clipping.
+the recall pass only with ``--recall``) and reports the share of the (detection, gt) pairs of the segments whose circumscribed circles meet, i.e.
+that go on towards the polygon clipping.  ``--rotated --recall`` sets the metadata's ``rotated_recall``: the split then holds the
+rotated recall pass as ``ar`` (ordering + sod_proposal_ar_rotated), with the minimum and maximum over the iterations beside the medians.
 """
 import argparse
 import hashlib
@@ -81,7 +82,10 @@ def main():
     ap.add_argument("--rotated", action="store_true", help="time the rotated-box evaluation (RotatedCOCOEvaluator)")
     ap.add_argument("--ratio-device", default=None,
                     help="take the gt ratios from structures.polygons.oriented_ratios on this device, through the metadata's ratio_device (COCOEvaluator only; default: the host loop)")
+    ap.add_argument("--recall", action="store_true", help="with --rotated: add the rotated recall pass (metadata rotated_recall) and report it as 'ar'")
     a = ap.parse_args()
+    if a.recall and not a.rotated:
+        ap.error("--recall applies to --rotated (COCOEvaluator always runs its recall pass)")
     if a.rotated and a.ratio_device is not None:
         ap.error("--ratio-device applies to COCOEvaluator, not to --rotated")
     dev = torch.device("cuda:0")
@@ -97,6 +101,8 @@ def main():
         t0 = time.perf_counter()
         if a.ratio_device is not None:
             MetadataCatalog.get("bench_coco_eval").ratio_device = a.ratio_device
+        if a.recall:
+            MetadataCatalog.get("bench_coco_eval").rotated_recall = True
         ev = (RotatedCOCOEvaluator if a.rotated else COCOEvaluator)("bench_coco_eval", None, False)
         t_gt = time.perf_counter() - t0
     flat = predictions_from_numpy(preds, dev)
@@ -116,9 +122,11 @@ def main():
         split["accumulate"].append(e["accumulate"].elapsed_time(e["end" if a.rotated else "ar"]))
         if not a.rotated:
             split["ar"].append(e["ar"].elapsed_time(e["end"]))
-        split["total"].append(e["match"].elapsed_time(e["end"]))
+        elif a.recall:
+            split["ar"].append(e["ar"].elapsed_time(e["ar_end"]))
+        split["total"].append(e["match"].elapsed_time(e["ar_end" if a.recall else "end"]))
     h = hashlib.sha256()
-    for arr in (ev.precision, ev.recall, ev.scores) + (() if a.rotated else (ev.recalls.numpy(),)):
+    for arr in (ev.precision, ev.recall, ev.scores) + (() if a.rotated and not a.recall else (ev.recalls.numpy(),)):
         h.update(np.ascontiguousarray(arr).tobytes())
     n_all, n_ours = (None, None) if a.no_profile else _launches(ev, flat)
     out = {
@@ -130,6 +138,9 @@ def main():
         "kernel_launches": n_all, "coco_kernel_launches": n_ours,
         "AP": res["bbox"]["AP"], **({} if a.rotated else {"AR@100": res["ar"]["AR@100"]}), "output_sha256": h.hexdigest()[:16],
     }
+    if a.recall:
+        out["device_ms_min_max"] = {k: [round(float(np.min(v)), 3), round(float(np.max(v)), 3)] for k, v in split.items() if v}
+        out["AR@100"] = res["ar"]["AR@100"]
     if a.rotated:
         pairs, near = _circle_share(ds, preds)
         out.update(metric="rotated_coco_eval_device_ms", AR100=float(ev.stats[8] * 100), segment_pairs=pairs,
